@@ -2,6 +2,7 @@
 """bench.py -- stereo pairs/s of the DiffuVolume hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sceneflow|kitti12|kitti15] [--batch B] [--height H] [--width W]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (SURVEY 8d "HOT") over one batch of synthetic stereo
 pairs per GPU, inputs already resident in HBM:
@@ -19,6 +20,9 @@ fails if fewer than N devices are visible.  It never silently measures fewer GPU
 Prints ONE JSON line (rank 0): the driver contract plus `roofline` (dominant kernel: the
 fp32-MFMA Winograd conv of the 32-channel layers, HIP-event timed inside the timed region) and `cpu_baseline`
 (the CPU oracle on a bounded sample of the same workload, rank 0, N=1 only).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (see `dump_outputs`) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -157,9 +161,14 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the hipGraph, end-to-end and config 4 / 5 side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "< 64 MB in all: arrays beyond their share are written as a fixed seeded sample)")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check of the N-process launch on CPU (gloo): rendezvous + one all-reduce, no GPU work")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     for k, v in WORKLOADS[a.workload]["defaults"].items():
         if getattr(a, k) is None:
             setattr(a, k, v)
@@ -241,6 +250,44 @@ def launcher_label() -> str:
     if os.environ.get("TORCHELASTIC_RUN_ID"):
         return "torchrun"
     return "env" if under_launcher() else "single"
+
+
+# --dump-outputs: bytes per array (the first one named, the prediction, gets the larger share); 24 + 3 x 12 MiB < 64 MB
+DUMP_FIRST_BYTES = 24 << 20
+DUMP_OTHER_BYTES = 12 << 20
+DUMP_MAX_ARRAYS = 4
+TIMED_SEED = 100                  # + rank: the generator state the timed steps start from
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` (name -> device tensor, in order, at most DUMP_MAX_ARRAYS) as out_dir/<name>.npy and return what was
+    written.  Floating tensors keep float32 / float64 (anything else becomes float64).  An array larger than its share
+    is written as a sample: the flat elements at a fixed set of indices, drawn from a CPU generator seeded by the
+    array's name and its shape, sorted -- the same positions on every run with the same arguments."""
+    import zlib
+    import numpy as np
+    assert len(arrays) <= DUMP_MAX_ARRAYS
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    info = {}
+    for i, (name, t) in enumerate(arrays.items()):
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        cap = (DUMP_FIRST_BYTES if i == 0 else DUMP_OTHER_BYTES) // t.element_size()
+        n = t.numel()
+        if n <= cap:
+            host = t.cpu().contiguous().numpy()
+            sampled = None
+        else:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(zlib.crc32(f"{name}{tuple(t.shape)}".encode()) & 0x7FFFFFFF)
+            idx = torch.randint(n, (cap,), generator=g).sort().values
+            host = t.reshape(-1)[idx.to(t.device)].cpu().numpy()
+            sampled = cap
+        np.save(out_dir / f"{name}.npy", host)
+        info[name] = {"shape": list(t.shape), "dtype": str(host.dtype), "sampled_elements": sampled}
+    return {"dir": str(out_dir), "arrays": info}
 
 
 def make_inputs(batch, h, w, seed, device):
@@ -569,31 +616,41 @@ def main_flavour(a, rank, world, device):
     model, step_fn, what = flavour_workload(a, rank, device)
     acc = M.MetricAccumulator(device)
 
-    def step():
+    def step(keep=False):
         pred, gt = step_fn()
-        acc.update_sums(M.image_sums(pred, gt, (gt < 192) & (gt > 0)))
+        sums = M.image_sums(pred, gt, (gt < 192) & (gt > 0))
+        acc.update_sums(sums)
+        return {"prediction": pred, "image_metric_sums": sums} if keep else None
 
-    def timed_region(timer):
+    def timed_region(timer, keep_last=False):
         KernelTimer.active = timer
         torch.cuda.synchronize()
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step()
+        last = None
+        for i in range(a.steps):
+            last = step(keep=keep_last and i == a.steps - 1)
         e = acc.reduce()
         torch.cuda.synchronize()
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
         d = time.perf_counter() - t0
         KernelTimer.active = None
-        return D.barrier_and_max(d, device), e
+        return D.barrier_and_max(d, device), e, last
 
+    dumped = None
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
         acc = M.MetricAccumulator(device)
-        dt, epe = timed_region(None)
+        # the DDIM loop's randn / rand draws come from the device generator: seeded here, so that the timed steps compute
+        # the same thing on every run with the same arguments, whatever the warm-up did
+        torch.manual_seed(TIMED_SEED + rank)
+        dt, epe, last = timed_region(None, keep_last=a.dump_outputs is not None)
+        if last is not None and rank == 0:
+            dumped = dump_outputs(a.dump_outputs, last)
+        del last
         timer = None
         if not a.no_kernel_timer:
             acc = M.MetricAccumulator(device)
@@ -624,6 +681,8 @@ def main_flavour(a, rank, world, device):
            "cpu_baseline": None,
            "cpu_baseline_note": "timed for the headline workload only (python bench.py); the oracles of configs 4 / 5 are "
                                 "the checkers of tests/, minutes per pair at these sizes"}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and timer is not None:
         ks = timer.summary()
         mf = {k: v for k, v in ks.items() if v["issued_flops"] > 0}
@@ -699,41 +758,52 @@ def main():
     mask = (x["gt"] < 192) & (x["gt"] > 0)
     acc = M.MetricAccumulator(device)
 
-    def step(tape=None):
-        final, stack, _ = hot_path(model, x, tape)
-        acc.update_sums(M.image_sums(final, x["gt"], mask))      # this rank's shard of the step's global batch
-        return final, stack
+    def step(tape=None, keep=False):
+        final, stack, gwc = hot_path(model, x, tape)
+        sums = M.image_sums(final, x["gt"], mask)
+        acc.update_sums(sums)      # this rank's shard of the step's global batch
+        # what a caller of the hot path receives (kept for --dump-outputs on the last timed step only)
+        return {"final_disparity": final, "ddim_stack": stack, "gwc_volume": gwc, "image_metric_sums": sums} if keep else None
 
-    def timed_region(timer):
-        """K steps between barriers + synchronize; returns the MAX over ranks of the wall time."""
+    def timed_region(timer, keep_last=False):
+        """K steps between barriers + synchronize; returns the MAX over ranks of the wall time, the reduced metrics and
+        (keep_last) the outputs of the last step."""
         KernelTimer.active = timer
         torch.cuda.synchronize()
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step()
+        last = None
+        for i in range(a.steps):
+            last = step(keep=keep_last and i == a.steps - 1)
         e = acc.reduce()                 # the one collective of the path (48 bytes per batch, SUM over RCCL)
         torch.cuda.synchronize()
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
         d = time.perf_counter() - t0
         KernelTimer.active = None
-        return D.barrier_and_max(d, device), e
+        return D.barrier_and_max(d, device), e, last
 
+    dumped = None
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
         # pass 1: `value` -- nothing but the hot path in the timed region (no per-kernel events)
         acc = M.MetricAccumulator(device)
-        dt, epe = timed_region(None)
+        # the DDIM loop's randn / rand draws come from the device generator: seeded here, so that the timed steps compute
+        # the same thing on every run with the same arguments, whatever the warm-up did
+        torch.manual_seed(TIMED_SEED + rank)
+        dt, epe, last = timed_region(None, keep_last=a.dump_outputs is not None)
+        if last is not None and rank == 0:
+            dumped = dump_outputs(a.dump_outputs, last)
+        del last
         # pass 2 (rank 0's figures are the ones reported): the same K steps again with a HIP-event pair around every
         # kernel for the roofline / per-kernel numbers; its wall time is reported beside `value`, never as `value`
         timer, dt_events = None, None
         if not a.no_kernel_timer:
             acc = M.MetricAccumulator(device)
             timer = KernelTimer()
-            dt_events, _ = timed_region(timer)
+            dt_events, _, _ = timed_region(timer)
 
     pairs = a.batch * world * a.steps
     value = pairs / dt
@@ -768,6 +838,8 @@ def main():
         # 2.25x fewer multiplies); the hardware figure is `mfma_f32_issued_frac_whole_path` below
         "algorithmic_flop_rate_over_mfma_f32_peak_whole_path": value / world * ALGO_FLOP_PER_PAIR / (PEAK_MFMA_F32_TFLOPS * 1e12),
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and timer is not None:
         ks = timer.summary()
         # dominant kernel: `avg_ms` is the average rocprofv3 --stats reports for that kernel name in the same command

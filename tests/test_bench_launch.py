@@ -148,3 +148,30 @@ def test_device_count_without_the_runtime():
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def test_dump_outputs_writes_small_arrays_whole_and_samples_large_ones(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files under 64 MB in all; an array beyond its share is a sample taken at the
+    same positions on every call (two builds are compared output for output)."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    big = torch.arange(2 * mod.DUMP_OTHER_BYTES // 4, dtype=torch.float32).reshape(2, -1)
+    arrays = {"pred": torch.rand(3, 5, 7), "big": big, "sums": torch.ones(3, 8, dtype=torch.float64),
+              "flags": torch.tensor([1, 0, 1])}
+    info = mod.dump_outputs(tmp_path / "a", arrays)
+    mod.dump_outputs(tmp_path / "b", arrays)
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert [f.stem for f in files] == sorted(arrays)
+    assert sum(f.stat().st_size for f in files) < 64e6
+    pred = np.load(tmp_path / "a" / "pred.npy")
+    assert pred.dtype == np.float32 and np.array_equal(pred, arrays["pred"].numpy())
+    assert np.load(tmp_path / "a" / "sums.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "flags.npy").dtype == np.float64
+    sample = np.load(tmp_path / "a" / "big.npy")
+    assert info["arrays"]["big"]["sampled_elements"] == sample.size == mod.DUMP_OTHER_BYTES // 4
+    assert np.all(np.diff(sample) >= 0) and np.array_equal(sample, big.reshape(-1)[sample.astype(np.int64)].numpy())
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "big.npy"))
