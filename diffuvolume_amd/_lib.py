@@ -107,6 +107,14 @@ SIGNATURES = {
     "dv_context_upsample_f32": (c_int, [P, P, P, I, I, I, c_float, I, P]),
     "dv_allpairs_corr_f32": (c_int, [P, P, P, P, I, I, I, I, I, P]),
     "dv_conv2d_1in_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
+    "dv_conv2d_1in_f16": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
+    "dv_conv2d_f16_packed_bytes": (c_size_t, [I, I, I]),
+    "dv_conv2d_f16_pack_weights": (c_int, [P, P, I, I, I, P]),
+    "dv_conv2d_f16_auto_kslices": (c_int, [I, I, I, I, I]),
+    "dv_conv2d_f16_cat": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "dv_conv2d_f16_cat_ksplit": (c_int, [P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "dv_conv2d_f16_cat_pair": (c_int, [P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "dv_conv2d_f16_cat_pair_ksplit": (c_int, [P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "dv_resize_bilinear_ac_f32": (c_int, [P, P, I, I, I, I, I, P]),
     "dv_avg_pool3s2_f32": (c_int, [P, P, I, I, I, P]),
     "dv_conv2d_fewin_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

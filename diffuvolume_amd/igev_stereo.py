@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .igev_stereo_ddim import IGEVStereo_ddim, context_upsample, hip_sequential
+from .igev_stereo_ddim import IGEVStereo_ddim, context_upsample, hip_sequential, round_gru_inputs_f16
 
 _SCHEDULE = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
              "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
@@ -43,15 +43,19 @@ class IGEVStereo(IGEVStereo_ddim):
             unit = torch.ones((b, self.args.max_disp // 4, h, w), dtype=torch.float32, device=init_disp.device)
             n, slow = self.args.n_gru_layers, self.args.slow_fast_gru
             disp, disp_preds, disp_up = init_disp, [], None
+            amp = bool(getattr(self.args, "mixed_precision", False))     # read at every forward, as the reference does
+            if amp:
+                net_list, inp_list = round_gru_inputs_f16(net_list, inp_list)
             for itr in range(iters):                     # :203-214
                 geo_feat = geo_fn(disp, coords, unit)
-                if n == 3 and slow:
-                    net_list = self.update_block(net_list, inp_list, iter16=True, iter08=False, iter04=False, update=False)
-                if n >= 2 and slow:
-                    net_list = self.update_block(net_list, inp_list, iter16=n == 3, iter08=True, iter04=False, update=False)
                 last = itr == iters - 1
-                net_list, mask_feat_4, delta_disp = self.update_block(net_list, inp_list, geo_feat, disp, iter16=n == 3,
-                                                                      iter08=n >= 2, mask=last or not test_mode)
+                with torch.autocast("cuda", dtype=torch.float16, enabled=amp):      # :202 (the update block only)
+                    if n == 3 and slow:
+                        net_list = self.update_block(net_list, inp_list, iter16=True, iter08=False, iter04=False, update=False)
+                    if n >= 2 and slow:
+                        net_list = self.update_block(net_list, inp_list, iter16=n == 3, iter08=True, iter04=False, update=False)
+                    net_list, mask_feat_4, delta_disp = self.update_block(net_list, inp_list, geo_feat, disp, iter16=n == 3,
+                                                                          iter08=n >= 2, mask=last or not test_mode)
                 disp = disp + delta_disp
                 if test_mode and not last:
                     continue

@@ -51,14 +51,24 @@ class DynamicHead180(nn.Module):
         return noisy + self.shift(t).unsqueeze(-1).unsqueeze(-1)
 
 
+def round_gru_inputs_f16(net_list, inp_list):
+    """The hidden states and the context terms cz / cr / cq rounded to fp16 values (kept as float32) when the GRU loop
+    starts under `mixed_precision`: the reference's front produces them under autocast as fp16 tensors (`torch.tanh`,
+    `torch.relu` and `context_zqr_convs`, igev_stereo_ddim.py:366-400) while this build's front stays float32 (it runs
+    once per forward, and float32 is closer to the exact result).  Idempotent on fp16-exact values."""
+    r = lambda t: t.half().float() if isinstance(t, torch.Tensor) else t
+    return [r(t) for t in net_list], [[r(t) for t in trio] for trio in inp_list]
+
+
 class IGEVDiffusionLoop:
     def __init__(self, time_embedding: DynamicHead180, update_block: Callable, upsample_disp: Callable,
                  n_gru_layers: int = 3, slow_fast_gru: bool = False, sampling_timesteps: int = 2,
-                 ensemble_cof: Sequence[float] = (0.6, 0.1, 0.3)):
+                 ensemble_cof: Sequence[float] = (0.6, 0.1, 0.3), mixed_precision: bool = False):
         if len(ensemble_cof) != sampling_timesteps + 1:
             raise ValueError("ensemble_cof needs sampling_timesteps + 1 entries")
         self.time_embedding, self.update_block, self.upsample_disp = time_embedding, update_block, upsample_disp
         self.n_gru_layers, self.slow_fast_gru = n_gru_layers, slow_fast_gru
+        self.mixed_precision = bool(mixed_precision)     # the update block under fp16 autocast (igev_stereo_ddim.py:242)
         self.num_timesteps, self.sampling_timesteps, self.eta = 1000, sampling_timesteps, 1.0
         self.ensemble_cof = tuple(float(c) for c in ensemble_cof)
         ac = torch.cumprod(1.0 - cosine_beta_schedule(1000), dim=0)
@@ -97,17 +107,17 @@ class IGEVDiffusionLoop:
     # 0.06-0.1 ms kernels), a replay only adds the state copies and the capture.  OPT-IN: `use_graph` / DV_IGEV_GRAPH=1.
     use_graph = os.environ.get("DV_IGEV_GRAPH", "0") == "1"
     _graph = None
-    _graph_warm = False
+    _graph_warm = frozenset()           # the precision modes whose eager warm-up pass has run
 
     def _gru_iterations(self, coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, n01f, stem_2x):
         ok = (self.use_graph and flow_init is None and coords1.is_cuda and not torch.cuda.is_current_stream_capturing()
               and all(isinstance(t, torch.Tensor) for t in net_list))
         if not ok:
             return self._gru_iterations_eager(coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, n01f, stem_2x)
-        if not self._graph_warm:           # plans / packed weights are built lazily on the first pass: never inside a capture
-            self._graph_warm = True
+        if self.mixed_precision not in self._graph_warm:   # plans / packed weights (fp32 and fp16 ones apart) are built
+            self._graph_warm = self._graph_warm | {self.mixed_precision}     # lazily on a mode's first pass: never in a capture
             return self._gru_iterations_eager(coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, n01f, stem_2x)
-        key = (id(corr_fn), id(inp_list), iters, tuple(coords1.shape), coords0.data_ptr(), id(stem_2x))
+        key = (id(corr_fn), id(inp_list), iters, tuple(coords1.shape), coords0.data_ptr(), id(stem_2x), self.mixed_precision)
         g = self._graph
         if g is None or g["key"] != key:
             self._graph = g = None                                   # drop the previous graph (and its memory pool) first
@@ -140,19 +150,25 @@ class IGEVDiffusionLoop:
         # (The update block runs lookup + motion encoder on a side stream beside gru16 / gru08: update.py, OVERLAP.)
         from .update import BasicMultiUpdateBlock
         skip_mask = isinstance(self.update_block, BasicMultiUpdateBlock)
+        amp = self.mixed_precision
+        if amp:
+            net_list, inp_list = round_gru_inputs_f16(net_list, inp_list)
         for itr in range(iters):
             flow = coords1 - coords0
             # this build's update block takes the lookup as a request and runs it fused with its first convolution
             corr = corr_fn.request(flow, coords1, n01f) if (skip_mask and hasattr(corr_fn, "request")) else corr_fn(flow, coords1, n01f)
-            if self.n_gru_layers == 3 and self.slow_fast_gru:
-                net_list = self.update_block(net_list, inp_list, iter32=True, iter16=False, iter08=False, update=False)
-            if self.n_gru_layers >= 2 and self.slow_fast_gru:
-                net_list = self.update_block(net_list, inp_list, iter32=self.n_gru_layers == 3, iter16=True,
-                                             iter08=False, update=False)
-            net_list, up_mask, delta_flow = self.update_block(net_list, inp_list, corr, flow,
-                                                              iter16=self.n_gru_layers == 3,
-                                                              iter08=self.n_gru_layers >= 2,
-                                                              **({"mask": itr == iters - 1} if skip_mask else {}))
+            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):      # :242-246
+                if self.n_gru_layers == 3 and self.slow_fast_gru:
+                    net_list = self.update_block(net_list, inp_list, iter32=True, iter16=False, iter08=False, update=False)
+                if self.n_gru_layers >= 2 and self.slow_fast_gru:
+                    net_list = self.update_block(net_list, inp_list, iter32=self.n_gru_layers == 3, iter16=True,
+                                                 iter08=False, update=False)
+                net_list, up_mask, delta_flow = self.update_block(net_list, inp_list, corr, flow,
+                                                                  iter16=self.n_gru_layers == 3,
+                                                                  iter08=self.n_gru_layers >= 2,
+                                                                  **({"mask": itr == iters - 1} if skip_mask else {}))
+            if amp:                # an update block that returns fp16 tensors (the reference's own): float32 from here on
+                up_mask, delta_flow = (None if up_mask is None else up_mask.float()), delta_flow.float()
             coords1 = coords1 + delta_flow
             if itr == iters - 1:
                 flow_up = self.upsample_disp(coords1 - coords0, up_mask, stem_2x)[:, :1]
@@ -784,7 +800,10 @@ class Feature(nn.Module):
 class IGEVStereo_ddim(nn.Module):
     """``IGEVStereo_ddim(args).forward(image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False)
     -> (pred, pred)`` (eval path, igev_stereo_ddim.py:361-427).  ``args``: hidden_dims, n_gru_layers, n_downsample,
-    corr_levels, corr_radius, slow_fast_gru, max_disp, mixed_precision (must be False: the HIP path is fp32).
+    corr_levels, corr_radius, slow_fast_gru, max_disp, mixed_precision.  ``mixed_precision=True`` runs the update block
+    of every GRU iteration under fp16 autocast like the reference (:242-246): its convolutions on fp16 MFMA with the
+    reference's fp16 rounding points (csrc/conv2d_f16.hip); the front, hourglass(8), the geometry lookup,
+    ``upsample_disp`` and the DDIM state stay float32.  The flag is read at every forward.
     ``feature``: the MobileNetV2 feature pyramid (``Feature(backbone)``); None = the reference's own construction from
     timm's pretrained ``mobilenetv2_100`` (core/extractor.py:327-335), which needs ``timm`` to be importable;
     ``cnet``: optional replacement for the context encoder.  ``sampling_timesteps`` / ``ensemble_cof`` are
@@ -805,8 +824,6 @@ class IGEVStereo_ddim(nn.Module):
                     "pretrained=True, features_only=True) like the reference (core/extractor.py:331); timm is not "
                     "importable here -- pass feature=Feature(backbone) (a timm model or synth.StubMobileNetV2())")
             feature = Feature(timm.create_model("mobilenetv2_100", pretrained=True, features_only=True))
-        if getattr(args, "mixed_precision", False):
-            raise _lib.DiffuVolumeError("the HIP path computes in fp32: mixed_precision must be False")
         self.args = args
         self.scale = 1.0
         self.num_timesteps = 1000
@@ -930,7 +947,8 @@ class IGEVStereo_ddim(nn.Module):
     def _loop(self):
         return IGEVDiffusionLoop(self.time_embedding, self.update_block, self.upsample_disp,
                                  n_gru_layers=self.args.n_gru_layers, slow_fast_gru=self.args.slow_fast_gru,
-                                 sampling_timesteps=self.sampling_timesteps, ensemble_cof=self.ensemble_cof)
+                                 sampling_timesteps=self.sampling_timesteps, ensemble_cof=self.ensemble_cof,
+                                 mixed_precision=bool(getattr(self.args, "mixed_precision", False)))
 
     @torch.no_grad()
     def model_predictions(self, coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, noise, t, stem_2x):

@@ -22,7 +22,7 @@ from .profiling import S2PP_MULT_REDUCTION, WINO3_MULT_REDUCTION, WINO_MULT_REDU
 
 __all__ = ["build_gwc_volume", "build_concat_volume", "build_concat_attention_volume", "AttentionConcatVolume",
            "volume_factors",
-           "disparity_regression", "upsample_softmax_regress", "Conv3dPlan", "Conv2dPlan", "Deconv3dPlan",
+           "disparity_regression", "upsample_softmax_regress", "Conv3dPlan", "Conv2dPlan", "Conv2dF16Plan", "Deconv3dPlan",
            "window_attention", "feature_gate", "softmax_regress", "refine_inputs", "patch_volume", "ACT_NONE", "ACT_RELU", "ACT_MISH", "ACT_LEAKY", "ACT_SIGMOID", "ACT_TANH"]
 
 ACT_NONE, ACT_RELU, ACT_MISH, ACT_LEAKY, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4, 5     # last two: 2-D convs only
@@ -736,6 +736,105 @@ class Conv2dPairPlan:
                                                                      b, h, w, self.c1, self.c2, self.act, _lib.stream_ptr()),
                                      "dv_conv2d_wino_cat_pair_f32"), issued=2.0 * n_out * self.cin * 9 / WINO_MULT_REDUCTION)
         return outs[0], outs[1]
+
+
+class Conv2dF16Plan:
+    """The fp16-autocast form of a stride-1, dilation-1 Conv2d(k 3 or 1) + bias [+ residual] [+ activation] [+ ConvGRU
+    gate arithmetic] (csrc/conv2d_f16.hip, v_mfma_f32_16x16x32_f16): what IGEV's update block computes under
+    `autocast(enabled=args.mixed_precision)` (KITTI15/core/update.py:26-142, igev_stereo_ddim.py:242-246).  Input,
+    weight and bias are rounded to fp16, products accumulate in fp32, the output and every epilogue op's result are
+    rounded to fp16; tensors stay float32 holding fp16-exact values.
+
+    Selected per plan by the update block (never through DV_CONV_PRECISION, which steers the 3-D convolutions).  With
+    ``pair=(w2, b2)`` it is the two-gate launch of ConvGRU's convz | convr: ``__call__`` then returns two tensors and takes
+    ``residual`` / ``mul`` as pairs, like Conv2dPairPlan."""
+
+    KSPLIT = True
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
+                 pair: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
+        w = _dev_f32(weight.detach(), "weight")
+        self.c1, self.cin, self.k = w.shape[0], w.shape[1], w.shape[2]
+        if tuple(w.shape[2:]) != (self.k, self.k) or self.k not in (1, 3):
+            raise _lib.DiffuVolumeError(f"unsupported Conv2d kernel {tuple(w.shape[2:])} for the fp16 path")
+        self.act, self.c2 = act, 0
+        biases = [bias]
+        if pair is not None:
+            w2 = _dev_f32(pair[0].detach(), "weight")
+            if self.k != 3 or tuple(w2.shape[1:]) != tuple(w.shape[1:]):
+                raise _lib.DiffuVolumeError("pair launch: two 3x3 convolutions of the same input")
+            self.c2 = w2.shape[0]
+            w = torch.cat([w, w2], dim=0).contiguous()
+            biases.append(pair[1])
+        cout = self.c1 + self.c2
+        self.bias = None
+        if any(t is not None for t in biases):
+            sizes = [self.c1] + ([self.c2] if pair is not None else [])
+            self.bias = torch.cat([_dev_f32(t.detach(), "bias") if t is not None else
+                                   torch.zeros(n, dtype=torch.float32, device=w.device) for t, n in zip(biases, sizes)]).contiguous()
+        lib = _lib.load()
+        self.wpacked = torch.empty(lib.dv_conv2d_f16_packed_bytes(self.cin, cout, self.k), dtype=torch.uint8, device=w.device)
+        with torch.cuda.device(w.device):
+            _lib.check(lib.dv_conv2d_f16_pack_weights(w.data_ptr(), self.wpacked.data_ptr(), self.cin, cout, self.k,
+                                                      _lib.stream_ptr()), "conv2d f16 weight packing")
+
+    def __call__(self, x, residual=None, mul=None, blend=None):
+        parts = [_dev_f32(t, "x") for t in (x if isinstance(x, (list, tuple)) else [x])]
+        b, _, h, w = parts[0].shape
+        if not 1 <= len(parts) <= 4 or any(t.shape[0] != b or t.shape[2:] != parts[0].shape[2:] for t in parts):
+            raise RuntimeError("virtual concatenation: 1..4 tensors with equal batch and spatial size")
+        if sum(t.shape[1] for t in parts) != self.cin:
+            raise RuntimeError(f"expected {self.cin} input channels, got {sum(t.shape[1] for t in parts)}")
+        is_pair = self.c2 > 0
+        if not is_pair:
+            residual, mul = (residual,), (mul,)
+        elif blend is not None:
+            raise RuntimeError("the pair launch has no GRU blend")
+        outs = [torch.empty((b, c, h, w), dtype=torch.float32, device=parts[0].device)
+                for c in ((self.c1, self.c2) if is_pair else (self.c1,))]
+
+        def same(t, o, name):
+            if t is None:
+                return None
+            t = _dev_f32(t, name)
+            if tuple(t.shape) != tuple(o.shape):
+                raise RuntimeError(f"{name} shape mismatch")
+            return t
+        res = [same(residual[g], outs[g], "residual") for g in range(len(outs))]
+        mu = [same(mul[g], outs[g], "mul") for g in range(len(outs))]
+        bz, bh = (None, None) if blend is None else (same(blend[0], outs[0], "blend z"), same(blend[1], outs[0], "blend h"))
+        lib = _lib.load()
+        ptrs = (ctypes.c_void_p * len(parts))(*[t.data_ptr() for t in parts])
+        chans = (ctypes.c_int * len(parts))(*[t.shape[1] for t in parts])
+        cout = self.c1 + self.c2
+        n_out = b * cout * h * w
+        flops = 2.0 * n_out * self.cin * self.k ** 2
+        nb = 4.0 * (sum(t.numel() for t in parts) + n_out + sum(t.numel() for t in res + mu + [bz, bh] if t is not None))
+        # the K-split factor looks at ONE batch item (a shard of a batch reproduces the batch's bits, see Conv2dPlan)
+        ks = lib.dv_conv2d_f16_auto_kslices(self.cin, h, w, cout, self.k) if self.KSPLIT else 1
+        scratch = torch.empty(ks * n_out, dtype=torch.float32, device=parts[0].device) if ks > 1 else None
+        tag = f"conv2d_f16_k{self.k}_co{self.c1}" + (f"+{self.c2}" if is_pair else "") + ("_ksplit" if ks > 1 else "")
+        with torch.cuda.device(parts[0].device):
+            if is_pair:
+                args = (ptrs, chans, len(parts), self.wpacked.data_ptr(), _lib.ptr(self.bias), _lib.ptr(res[0]),
+                        _lib.ptr(mu[0]), outs[0].data_ptr(), _lib.ptr(res[1]), _lib.ptr(mu[1]), outs[1].data_ptr())
+                tail = (b, h, w, self.c1, self.c2, self.act, _lib.stream_ptr())
+                if ks > 1:
+                    fn = lambda: _lib.check(lib.dv_conv2d_f16_cat_pair_ksplit(*args, scratch.data_ptr(), ks, *tail),
+                                            "dv_conv2d_f16_cat_pair_ksplit")
+                else:
+                    fn = lambda: _lib.check(lib.dv_conv2d_f16_cat_pair(*args, *tail), "dv_conv2d_f16_cat_pair")
+            else:
+                args = (ptrs, chans, len(parts), self.wpacked.data_ptr(), _lib.ptr(self.bias), _lib.ptr(res[0]),
+                        _lib.ptr(mu[0]), _lib.ptr(bz), _lib.ptr(bh), outs[0].data_ptr())
+                tail = (b, h, w, self.c1, self.k, self.act, _lib.stream_ptr())
+                if ks > 1:
+                    fn = lambda: _lib.check(lib.dv_conv2d_f16_cat_ksplit(*args, scratch.data_ptr(), ks, *tail),
+                                            "dv_conv2d_f16_cat_ksplit")
+                else:
+                    fn = lambda: _lib.check(lib.dv_conv2d_f16_cat(*args, *tail), "dv_conv2d_f16_cat")
+            timed(tag, flops, nb, fn)
+        return (outs[0], outs[1]) if is_pair else outs[0]
 
 
 class Conv2dPlan:

@@ -7,6 +7,14 @@ arithmetic in the epilogues -- ``convr`` emits ``r*h`` directly, ``convq`` emits
 ConvGRU is three launches; the convolutions read ``[h | x...]`` as a virtual concatenation (``dv_conv2d_cat_f32``).  The 7x7 single-channel ``convd1``, the 3x3 average
 pooling and the bilinear interpolation between the three scales have their own small kernels (csrc/update_glue.hip); PyTorch
 writes the disparity channel into the motion features' 128th channel (the reference's ``torch.cat``).
+
+Under fp16 autocast (``torch.autocast("cuda", dtype=torch.float16)``: what the reference's
+``autocast(enabled=args.mixed_precision)`` around the update block turns on, igev_stereo_ddim.py:242-246) every module here
+runs its fp16 plans instead (csrc/conv2d_f16.hip, ``Conv2dF16Plan``; ``convd1`` on ``dv_conv2d_1in_f16``) with the rounding
+points of the reference's fp16 tensors: convolution operands and outputs, and every elementwise result of the fused
+epilogues, are rounded to fp16.  Storage stays float32 (fp16-exact values); fp16 input tensors are converted to float32
+on entry.  The motion features' channel 127 carries the float32 ``disp`` unrounded, as the reference's
+``torch.cat([out, disp])`` promotes to float32 under autocast (update.py:94).  bf16 autocast is refused.
 """
 from __future__ import annotations
 
@@ -15,27 +23,41 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan
+from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan
+
+
+def autocast_f16() -> bool:
+    """True when the caller runs under fp16 autocast on the GPU (the reference's ``autocast(enabled=mixed_precision)``):
+    the update block then computes with the fp16 rounding points.  bf16 autocast raises: the reference has no such
+    mode and computing fp32 instead would be silent."""
+    if not torch.is_autocast_enabled("cuda"):
+        return False
+    dt = torch.get_autocast_dtype("cuda")
+    if dt != torch.float16:
+        raise _lib.DiffuVolumeError(f"the IGEV update block supports fp16 autocast only (mixed_precision), got {dt}")
+    return True
 
 
 class _Planned(nn.Module):
-    """Plans (packed weights on the device) are rebuilt after .to() / load_state_dict()."""
+    """Plans (packed weights on the device) are rebuilt after .to() / load_state_dict(); the fp16-autocast plans
+    (``plans16``) are built lazily next to the fp32 ones and dropped by the same hooks."""
 
     def __init__(self):
         super().__init__()
         self._plans = None
+        self._plans16 = None
 
     def _apply(self, fn, *a, **k):
-        self._plans = None
+        self._plans = self._plans16 = None
         return super()._apply(fn, *a, **k)
 
     def _load_from_state_dict(self, *a, **k):      # runs for every sub-module, also when a parent is loaded
-        self._plans = None
+        self._plans = self._plans16 = None
         return super()._load_from_state_dict(*a, **k)
 
     def _replicate_for_data_parallel(self):        # nn.DataParallel replicas fold / pack their own weights
         replica = super()._replicate_for_data_parallel()
-        replica._plans = None
+        replica._plans = replica._plans16 = None
         return replica
 
     def plans(self):
@@ -43,9 +65,23 @@ class _Planned(nn.Module):
             self._plans = self._build()
         return self._plans
 
+    def plans16(self):
+        if self._plans16 is None:
+            self._plans16 = self._build16()
+        return self._plans16
+
 
 def _plan(conv: nn.Conv2d, act: int) -> Conv2dPlan:
     return Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
+
+
+def _plan16(conv: nn.Conv2d, act: int) -> Conv2dF16Plan:
+    return Conv2dF16Plan(conv.weight, conv.bias, act=act)
+
+
+def _f32(t):
+    """fp16 tensors an autocast caller hands over, as float32 (once, on entry)."""
+    return t.float() if isinstance(t, torch.Tensor) and t.dtype == torch.float16 else t
 
 
 class DispHead(_Planned):
@@ -59,9 +95,12 @@ class DispHead(_Planned):
     def _build(self):
         return _plan(self.conv1, ACT_RELU), _plan(self.conv2, ACT_NONE)
 
+    def _build16(self):
+        return _plan16(self.conv1, ACT_RELU), _plan16(self.conv2, ACT_NONE)
+
     def forward(self, x):
-        c1, c2 = self.plans()
-        return c2(c1(x))
+        c1, c2 = self.plans16() if autocast_f16() else self.plans()
+        return c2(c1(_f32(x)))
 
 
 class ConvGRU(_Planned):
@@ -81,8 +120,18 @@ class ConvGRU(_Planned):
         return (Conv2dPairPlan((self.convz.weight, self.convz.bias), (self.convr.weight, self.convr.bias), ACT_SIGMOID),
                 _plan(self.convq, ACT_TANH))
 
+    def _build16(self):
+        return (Conv2dF16Plan(self.convz.weight, self.convz.bias, ACT_SIGMOID, pair=(self.convr.weight, self.convr.bias)),
+                _plan16(self.convq, ACT_TANH))
+
     def forward(self, h, cz, cr, cq, *x_list):
-        pzr, pq = self.plans()
+        if autocast_f16():
+            # (the fp16 plans round z, r*h and the blend (1-z)*h + z*q at the reference's points; see csrc/conv2d_f16.hip)
+            pzr, pq = self.plans16()
+            h, cz, cr, cq = _f32(h), _f32(cz), _f32(cr), _f32(cq)
+            x_list = tuple(_f32(t) for t in x_list)
+        else:
+            pzr, pq = self.plans()
         if len(x_list) > 3:                             # the kernel takes four sources: [h | x1 | x2 | x3]
             x_list = (torch.cat(x_list[:-2], dim=1),) + tuple(x_list[-2:])
         hx = [h, *x_list]                               # torch.cat([h, x]) is never materialised
@@ -122,11 +171,20 @@ class BasicMotionEncoder(_Planned):
                                bias=torch.cat([b, b.new_zeros(1)]))
         return p
 
+    def _build16(self):
+        p = {n: _plan16(getattr(self, n), ACT_RELU) for n in ("convc1", "convc2", "convd2")}
+        w, b = self.conv.weight, self.conv.bias        # (the appended zero channel: see _build)
+        p["conv"] = Conv2dF16Plan(torch.cat([w, w.new_zeros((1,) + tuple(w.shape[1:]))]),
+                                  torch.cat([b, b.new_zeros(1)]), act=ACT_RELU)
+        return p
+
     def forward(self, disp, corr):
         return self.features(disp, corr)                # update.py:94 (the reference's return value)
 
     def features(self, disp, corr):
         """The motion features [B,128,h,w] = [conv output (127) | disp (1)], update.py:88-94."""
+        if autocast_f16():
+            return self._features16(_f32(disp), _f32(corr))
         p = self.plans()
         from .geometry_ddim import GeoLookupRequest
         if isinstance(corr, GeoLookupRequest):
@@ -142,7 +200,20 @@ class BasicMotionEncoder(_Planned):
         out[:, -1:].copy_(disp)
         return out
 
-    def _convd1(self, disp):
+    def _features16(self, disp, corr):
+        """features() under fp16 autocast: convc1 on the materialised lookup (the fused lookup + 1x1 of geo_lookup.hip
+        is the fp32 path's), every convolution on its fp16 plan; channel 127 = the float32 disp, unrounded."""
+        p = self.plans16()
+        from .geometry_ddim import GeoLookupRequest
+        if isinstance(corr, GeoLookupRequest):
+            corr = corr.materialize()
+        cor = p["convc2"](p["convc1"](corr))
+        disp_ = p["convd2"](self._convd1(disp, f16=True))
+        out = p["conv"]([cor, disp_])
+        out[:, -1:].copy_(disp)
+        return out
+
+    def _convd1(self, disp, f16=False):
         """relu(convd1(disp)): the 7x7 single-input-channel convolution on its own VALU kernel (MIOpen picks a naive
         solver for this shape: 0.7 ms per call at batch 4)."""
         if not _hip_ok(disp, "convd1"):
@@ -151,10 +222,10 @@ class BasicMotionEncoder(_Planned):
         b, _, h, w = disp.shape
         out = torch.empty((b, self.convd1.out_channels, h, w), dtype=torch.float32, device=disp.device)
         wt, bias = self.convd1.weight.contiguous(), self.convd1.bias
+        fn = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
         with torch.cuda.device(disp.device):
-            _lib.check(_lib.load().dv_conv2d_1in_f32(disp.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
-                                                     out.shape[1], int(wt.shape[-1]), ACT_RELU, _lib.stream_ptr()),
-                       "dv_conv2d_1in_f32")
+            _lib.check(getattr(_lib.load(), fn)(disp.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
+                                                out.shape[1], int(wt.shape[-1]), ACT_RELU, _lib.stream_ptr()), fn)
         return out
 
 
@@ -220,6 +291,9 @@ class BasicMultiUpdateBlock(_Planned):
     def _build(self):
         return _plan(self.mask_feat_4[0], ACT_RELU)
 
+    def _build16(self):
+        return _plan16(self.mask_feat_4[0], ACT_RELU)
+
     import os as _os
     OVERLAP = _os.environ.get("DV_IGEV_OVERLAP", "1") != "0"
     _streams = None
@@ -238,6 +312,12 @@ class BasicMultiUpdateBlock(_Planned):
         if self.training:
             raise NotImplementedError("the MI355X update block is inference-only (model.eval())")
         with torch.no_grad():
+            mixed = autocast_f16()
+            if mixed:             # an autocast caller's fp16 tensors: float32 once, here (the list objects are kept)
+                for i in range(len(net)):
+                    net[i] = _f32(net[i])
+                inp = [[_f32(t) for t in level] for level in inp]
+                corr, disp = _f32(corr), _f32(disp)
             mf = None
             if self.OVERLAP and iter04 and iter08 and corr is not None and disp.is_cuda and \
                     not torch.cuda.is_current_stream_capturing():
@@ -277,5 +357,5 @@ class BasicMultiUpdateBlock(_Planned):
             if not update:
                 return net
             delta_disp = self.disp_head(net[0])
-            mask_feat_4 = self.plans()(net[0]) if mask else None
+            mask_feat_4 = (self.plans16() if mixed else self.plans())(net[0]) if mask else None
         return net, mask_feat_4, delta_disp

@@ -441,8 +441,50 @@ int dv_context_upsample_f32(const float* disp_low, const float* weights, float* 
  *   in [BC,H,W] -> out [BC,(H-1)/2+1,(W-1)/2+1]. */
 int dv_conv2d_1in_f32(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cout,
                       int k, int act, dv_stream_t stream);
+/* dv_conv2d_1in_f16: dv_conv2d_1in_f32 under fp16 autocast (`convd1` with mixed_precision, update.py:86,:92 inside
+ *   igev_stereo_ddim.py:242-246's autocast region): input, weights and bias rounded to fp16, fp32 accumulation, the
+ *   convolution's output rounded to fp16 before the activation (sigmoid / tanh results rounded again).  fp32 storage. */
+int dv_conv2d_1in_f16(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cout,
+                      int k, int act, dv_stream_t stream);
 int dv_resize_bilinear_ac_f32(const float* in, float* out, int BC, int h, int w, int H, int W, dv_stream_t stream);
 int dv_avg_pool3s2_f32(const float* in, float* out, int BC, int H, int W, dv_stream_t stream);
+
+/* ---- IGEV's update block under fp16 autocast (csrc/conv2d_f16.hip): every 3x3 / 1x1 convolution of
+ * BasicMultiUpdateBlock with `mixed_precision=True` (KITTI15/core/update.py:26-142, run inside
+ * `autocast(enabled=self.args.mixed_precision)` at igev_stereo_ddim.py:242-246) as a direct implicit GEMM on
+ * v_mfma_f32_16x16x32_f16.  Input, weight and bias are rounded to fp16, products accumulate in fp32, the output is
+ * rounded to fp16, and every epilogue op rounds its result to fp16 again (what autocast's fp16 tensors do):
+ *   v = r(conv + r(bias)); v = r(v + residual); v = r(act(v)); v = r(v * mul); blend: v = r(r(r(1-z)*h) + r(z*v)).
+ * Storage is fp32 (fp16-exact values).  k in {1, 3}, dilation 1, stride 1, "same" padding; act NONE / RELU / SIGMOID /
+ * TANH.  `inputs` / `channels` are HOST arrays of n_inputs (1..4) sources read as one virtual channel concatenation
+ * (as dv_conv2d_cat_f32; any channel split).  residual / mul / blend_z / blend_h are [B,Cout,H,W] or NULL.
+ * dv_conv2d_f16_packed_bytes / dv_conv2d_f16_pack_weights: w [Cout,Cin,k,k] fp32 -> the kernel's fp16 image
+ *   (caller-allocated, packed_bytes bytes).
+ * dv_conv2d_f16_cat_pair: two 3x3 convolutions of the same input (ConvGRU's convz | convr, update.py:33-35) in one
+ *   launch: the weights of Cout1 + Cout2 channels packed back to back; channels < Cout1 go to out1 with residual1 /
+ *   mul1, the others to out2 with residual2 / mul2.
+ * dv_conv2d_f16_auto_kslices: the K-split factor for a launch of this shape (a function of ONE batch item: a shard of a
+ *   batch reproduces the batch's bits); > 1 means use the _ksplit forms with scratch of kslices * B * (Cout1 + Cout2)
+ *   * H * W floats.  The slices are summed in a fixed order (deterministic). */
+size_t dv_conv2d_f16_packed_bytes(int Cin, int Cout, int k);
+int dv_conv2d_f16_pack_weights(const float* w, void* wpacked, int Cin, int Cout, int k, dv_stream_t stream);
+int dv_conv2d_f16_auto_kslices(int Cin, int H, int W, int Cout, int k);
+int dv_conv2d_f16_cat(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+                      const float* bias, const float* residual, const float* mul, const float* blend_z,
+                      const float* blend_h, float* out, int B, int H, int W, int Cout, int k, int act,
+                      dv_stream_t stream);
+int dv_conv2d_f16_cat_ksplit(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+                             const float* bias, const float* residual, const float* mul, const float* blend_z,
+                             const float* blend_h, float* out, float* scratch, int kslices, int B, int H, int W,
+                             int Cout, int k, int act, dv_stream_t stream);
+int dv_conv2d_f16_cat_pair(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+                           const float* bias, const float* residual1, const float* mul1, float* out1,
+                           const float* residual2, const float* mul2, float* out2, int B, int H, int W, int Cout1,
+                           int Cout2, int act, dv_stream_t stream);
+int dv_conv2d_f16_cat_pair_ksplit(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+                                  const float* bias, const float* residual1, const float* mul1, float* out1,
+                                  const float* residual2, const float* mul2, float* out2, float* scratch, int kslices,
+                                  int B, int H, int W, int Cout1, int Cout2, int act, dv_stream_t stream);
 
 /* IGEV's once-per-pair 2-D front without MIOpen (csrc/igev_front.hip).
  * dv_conv2d_fewin_f32: nn.Conv2d(Cin <= 4, Cout, k in {3,5,7}, stride in {1,2}, padding=k/2) [+ bias] [+ folded eval
