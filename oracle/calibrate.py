@@ -82,3 +82,84 @@ def unpack(keys, values, lengths) -> Dict[str, torch.Tensor]:
         out[k] = values[o:o + n].clone().float()
         o += n
     return out
+
+
+# ---- the conditioned SceneFlow fixtures (oracle/make_golden_acv_conditioned.py) ------------------------------------
+ACV_WEIGHT_SEED = 1
+
+
+def conditioned_acv_state_dict(g) -> Dict[str, torch.Tensor]:
+    """The CONDITIONED SceneFlow weights of a tests/golden/acv_conditioned_*.npz fixture (``g``: the loaded fixture
+    dict): the synthetic ACVNet_DDIM state dict (seed 1) with the fixture's classifier gain and its BatchNorm
+    statistics in place of the random buffers."""
+    from diffuvolume_amd.acv_ddim import ACVNet_DDIM
+    from diffuvolume_amd.synth import synth_state_dict
+    sd = synth_state_dict(ACVNet_DDIM(192, False, False).state_dict(), seed=ACV_WEIGHT_SEED, logit_gain=float(g["gain"]))
+    stats = unpack(g["bn_keys"], g["bn_vals"], g["bn_lens"])
+    assert set(stats) <= set(sd), sorted(set(stats) - set(sd))
+    sd.update(stats)
+    return sd
+
+
+def conditioned_acv_inputs(batch: int, h: int, w: int, seed: int) -> Dict[str, torch.Tensor]:
+    """The structured input of a conditioned SceneFlow fixture, rebuilt from its seed (CPU, fp32): the hot path's
+    synthetic features (diffuvolume_amd.synth.synth_hot_inputs) and the attention-weighted concat volume built from
+    them by the oracle (acv_ddim.py:388-390)."""
+    from diffuvolume_amd.synth import synth_hot_inputs
+    x = synth_hot_inputs(batch, h, w, seed=seed)
+    x["vol"] = A.attention_concat_volume(x["att"], A.build_concat_volume(x["cl"], x["cr"], 48))
+    return x
+
+
+def f64_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Conv / attention weights in float64 (the time MLP stays fp32: its output is an input of the step)."""
+    return {k: (v.double() if v.is_floating_point() and not k.startswith("time_embedding") else v) for k, v in sd.items()}
+
+
+@torch.no_grad()
+def acv_float64_gate(sd, vol, used, x_T, tape_seed: int) -> Dict:
+    """How well conditioned the SceneFlow network is on one input: the 5-step loop of the fp32 oracle against the same
+    loop with float64 weights and activations, both from x_T with the same NoiseTape.  Returns the float64 step-1
+    disparity (``disp64``), the worst pixel |fp32 - fp64| of every step (``max_px``), the renewal decisions
+    (accumulated mask == 0) that differ between the two runs (``flips``) and the fp32 run itself (``final32`` /
+    ``stack32`` / ``trace32``)."""
+    from . import loop_parity as LP
+    final32, stack32, trace32 = LP.oracle_trajectory(A.ACVDiffusionOracle(sd), vol, used, x_T, tape_seed)
+    final64, stack64, trace64 = LP.oracle_trajectory(A.ACVDiffusionOracle(f64_state_dict(sd)), vol.double(),
+                                                     used.double(), x_T, tape_seed)
+    max_px = [float((stack32[i].double() - stack64[i]).abs().max()) for i in range(1, stack32.shape[0])]
+    flips = sum(int(((a["mask_out"] == 0) != (b["mask_out"] == 0)).sum()) for a, b in zip(trace32, trace64))
+    return {"disp64": stack64[1], "max_px": max_px, "final_max_px": float((final32.double() - final64).abs().max()),
+            "flips": flips, "final32": final32, "stack32": stack32, "trace32": trace32}
+
+
+@torch.no_grad()
+def pooled_loop_statistics(sd, vol, used, x_T, tape_seed: int, prefixes: Iterable[str]) -> Dict[str, torch.Tensor]:
+    """BatchNorm statistics of the SceneFlow DDIM-loop layers pooled over the five steps of the oracle's own trajectory:
+    step-1 calibration of ``sd`` (in place) at t = 999 from x_T, the oracle's 5-step run with those buffers, then the
+    batch statistics of every step taken with the step-1 buffers upstream, averaged as mean of means and mean of second
+    moments (one step at a time: a batch of five full-size volumes would need 10 GB).  Returns the pooled buffers under
+    ``prefixes``; ``sd`` keeps the step-1 buffers."""
+    from . import loop_parity as LP
+    b = vol.shape[0]
+    with calibrating_bn():
+        A.ACVDiffusionOracle(sd).model_predictions(vol, x_T, torch.full((b,), 999, dtype=torch.long))
+    _, _, trace = LP.oracle_trajectory(A.ACVDiffusionOracle(sd), vol, used, x_T, tape_seed)
+    acc = {}
+    for r in trace:
+        sdi = {k: v.clone() for k, v in sd.items()}
+        with calibrating_bn():
+            A.ACVDiffusionOracle(sdi).model_predictions(vol, r["img"].float(), torch.full((b,), r["time"], dtype=torch.long))
+        for k in bn_buffers(sdi, prefixes):
+            if not k.endswith("running_mean"):
+                continue
+            stem = k.rsplit(".", 1)[0]
+            m, var = sdi[stem + ".running_mean"].double(), sdi[stem + ".running_var"].double()
+            a = acc.setdefault(stem, [torch.zeros_like(m), torch.zeros_like(m)])
+            a[0] += m / len(trace)
+            a[1] += (var + m * m) / len(trace)
+    stats = {}
+    for stem, (m, m2) in acc.items():
+        stats[stem + ".running_mean"] = m.float()
+        stats[stem + ".running_var"] = (m2 - m * m).clamp(min=1e-6).float()
+    return stats

@@ -4,6 +4,8 @@ vectors captured from the reference.  Tolerances: the builders are compared bit 
 within 1e-5 relative of the layer's output scale (fp32 re-association only); the end-to-end
 DDIM loop as "bulk within 1e-3 px, mean within 1e-4" because hard renewal masks make single
 pixels chaotic."""
+from contextlib import contextmanager
+
 import numpy as np
 import pytest
 import torch
@@ -291,7 +293,7 @@ def test_deconv_oracle(cfg):
     assert rel_err(plan(dev(x), residual=dev(res)), torch.relu(y + res)) < 1e-5
 
 
-@pytest.mark.parametrize("tag", ["nopad", "pad", "padw"])
+@pytest.mark.parametrize("tag", ["nopad", "pad", "padw", "padh"])
 def test_window_attention_golden(tag):
     from diffuvolume_amd.acv_ddim import _WindowAttention
     g = load_golden(f"layer_attention_{tag}")
@@ -300,6 +302,54 @@ def test_window_attention_golden(tag):
                            dev(sd["final1x1.weight"]), dev(sd["final1x1.bias"]), heads=16)
     assert rel_err(y, g["y"]) < 2e-5
 
+
+
+def _attention_weights(seed):
+    from diffuvolume_amd.acv_ddim import _WindowAttention
+    return {"a." + k: v for k, v in synth_state_dict(_WindowAttention(128, 16).state_dict(), seed=seed).items()}
+
+
+def _window_attention_hip(x, sd):
+    return S.window_attention(dev(x), dev(sd["a.qkv_3d.weight"]), dev(sd["a.qkv_3d.bias"]), dev(sd["a.final1x1.weight"]),
+                              dev(sd["a.final1x1.bias"]), heads=16)
+
+
+@pytest.mark.parametrize("shape,gain", [((1, 128, 12, 32, 60), 1.0),    # the full-size bottleneck: 360 windows
+                                        ((2, 128, 12, 6, 20), 1.0),     # H padded only: no mask (reference quirk)
+                                        ((2, 128, 4, 5, 7), 1.0),       # H and W padded, batch 2: masked
+                                        ((1, 128, 8, 4, 4), 1.0),       # two depth windows, one in-plane window
+                                        ((2, 128, 12, 6, 20), 20.0)])   # logits up to 1.5e3 (3.6 at x1)
+def test_window_attention_vs_float64(shape, gain):
+    """csrc/window_attn.hip against the oracle's attention_block (SceneFlow/models/submodule.py:398-429) evaluated in
+    float64: the kernel's error relative to the output scale is at most 2x the fp32 oracle's own error + 1e-6.  Padded
+    tokens are zero inputs that still take part in the attention unless both H and W are padded (the reference's mask
+    quirk), which the oracle states as the reference does."""
+    sd = _attention_weights(25)
+    x = torch.randn(*shape, generator=_gen(25, f"{shape}")) * gain
+    sd64 = {k: v.double() for k, v in sd.items()}
+    y64 = O.attention_block(x.double(), sd64, "a")
+    y32 = O.attention_block(x, sd, "a")
+    y = _window_attention_hip(x, sd).cpu()
+    scale = float(y64.abs().max())
+    e_hip = float((y.double() - y64).abs().max()) / scale
+    e_orc = float((y32.double() - y64).abs().max()) / scale
+    print(f"window attention {shape} x{gain}: error vs float64 / output scale: HIP {e_hip:.2e}, fp32 oracle {e_orc:.2e}")
+    assert e_hip <= 2 * e_orc + 1e-6, (e_hip, e_orc)
+
+
+def test_window_attention_windows_are_independent():
+    """Full-size bottleneck [1,128,12,32,60]: changing the input inside one 4x4x4 window changes nothing outside it,
+    bit for bit (windows do not see each other, and the kernel does not mix them)."""
+    sd = _attention_weights(26)
+    x = torch.randn(1, 128, 12, 32, 60, generator=_gen(26, "x"))
+    x2 = x.clone()
+    win = (slice(None), slice(None), slice(4, 8), slice(16, 20), slice(36, 40))
+    x2[win] = torch.randn(x2[win].shape, generator=_gen(26, "win")) * 3
+    y, y2 = _window_attention_hip(x, sd), _window_attention_hip(x2, sd)
+    inside = torch.zeros(y.shape, dtype=torch.bool, device=y.device)
+    inside[win] = True
+    assert torch.equal(y[~inside], y2[~inside])
+    assert not torch.equal(y[inside], y2[inside])
 
 def test_hourglass_golden():
     from diffuvolume_amd.acv_ddim import Hourglass, _HourglassPlan
@@ -363,24 +413,55 @@ def test_aggregation_cost_parity(model, acv_state_dict):
     assert e_hip < 3 * e_ref, (e_hip, e_ref)
 
 
+@contextmanager
+def _wino3(on):
+    """Routing of the 3x3x3 stride-1 layers with >= 64 input channels: the F(2x2x2,3x3x3) kernel (shipped) or the in-plane
+    F(2x2,3x3) kernel."""
+    keep = S.Conv3dPlan.WINO3
+    S.Conv3dPlan.WINO3 = on
+    try:
+        yield
+    finally:
+        S.Conv3dPlan.WINO3 = keep
+
+
+# share of the 8 192 pixels beyond 1e-3 px between the reference's fp32 step 1 and HIP's on the unconditioned fixture:
+# the contract's 1e-3 with the in-plane kernel everywhere (measured 7 pixels), a ceiling of 1.25e-3 with the shipped
+# routing (measured 9 pixels); the contract itself is asserted on the conditioned network, test_gpu_acv_conditioned.py
+STEP1_SHARE = {True: 1.25e-3, False: 1e-3}
+
+
+def _assert_step1_vs_reference(d, wino3):
+    share = float((d > 1e-3).float().mean())
+    print(f"step 1 vs reference, {'F(2x2x2)' if wino3 else 'in-plane'} routing: {int((d > 1e-3).sum())} of {d.numel()} "
+          f"pixels beyond 1e-3 px, mean {float(d.mean()):.2e}, max {float(d.max()):.2e} px")
+    assert float(d.mean()) < 2e-4 and float(d.max()) < 2e-3 and share <= STEP1_SHARE[wino3], \
+        (wino3, float(d.mean()), float(d.max()), share)
+
+
 def test_model_predictions_golden(model, acv_state_dict):
     """One volume-filter step against the reference's own fp32 output AND against a float64 evaluation of the same step
-    (oracle/acv_oracle.py in float64): north-star bars -- disparity within 1e-3 px, EPE within 1e-4.
-    The soft-argmax amplifies cost error by the spread of the distribution, |d disp| <= unc * max|d cost|; with random
-    weights the spread is large, and the reference's fp32 output is itself up to 9.5e-4 px from the float64 value.  So:
+    (oracle/acv_oracle.py in float64).  This fixture's network has random BatchNorm buffers: the soft-argmax spreads over
+    30-50 px and amplifies cost error by that spread, |d disp| <= unc * max|d cost|, so the reference's fp32 output is
+    itself up to 9.5e-4 px from the float64 value.  The contract's raw bars against the reference's outputs are asserted
+    on the conditioned network (tests/test_gpu_acv_conditioned.py); here:
       * against float64 (the value both fp32 paths approximate): EVERY pixel within 1e-3 px, and a mean error no larger
         than 1.1 x the reference's own (measured: reference 6.8e-5 mean / 9.5e-4 max; HIP 6.8e-5 / 7.0e-4);
       * against the reference's fp32 output, i.e. between two fp32 evaluations whose errors can have opposite signs:
-        mean < 2e-4, 99th percentile < 1e-3, no pixel beyond 2e-3, at most 0.25 % of the pixels beyond 1e-3 (measured
-        8.6e-5 / 5.7e-4 / 1.5e-3 / 0.11 %; with the in-plane Winograd kernel in every layer 8.4e-5 / 5.4e-4 / 1.4e-3 /
-        0.085 % -- the F(2x2x2) kernel of the 64- and 128-channel layers is the more accurate one against float64,
-        tests/test_gpu_wino3.py, but lands on the other side of the reference on two more of the 8 192 pixels)."""
+        mean < 2e-4, 99th percentile < 1e-3, no pixel beyond 2e-3, and at most STEP1_SHARE of the pixels beyond 1e-3 px.
+        Measured with the shipped routing 8.6e-5 / 5.7e-4 / 1.5e-3 / 9 pixels (0.11 %, ceiling 1.25e-3), with the in-plane
+        Winograd kernel in every layer 8.4e-5 / 5.4e-4 / 1.4e-3 / 7 pixels (0.085 %, the contract's 1e-3) -- the
+        F(2x2x2) kernel of the 64- and 128-channel layers is the more accurate one against float64,
+        tests/test_gpu_wino3.py, but lands on the other side of the reference on two more pixels."""
+    g = load_golden("model_predictions")
+    with _wino3(False):
+        pred_ip = model.model_predictions(dev(_volume(g["vol_seed"])), dev(g["x_T"]), dev(g["t"]))[2]
+    _assert_step1_vs_reference((pred_ip.cpu() - g["pred"]).abs(), False)
     g = load_golden("model_predictions")
     pn, xs, pred, handle = model.model_predictions(dev(_volume(g["vol_seed"])), dev(g["x_T"]), dev(g["t"]))
     assert pn.dtype == torch.float64 and xs.dtype == torch.float32
     d = (pred.cpu() - g["pred"]).abs()
-    assert float(d.mean()) < 2e-4 and float(d.max()) < 2e-3 and float((d > 1e-3).float().mean()) <= 2.5e-3, \
-        (float(d.mean()), float(d.max()), float((d > 1e-3).float().mean()))
+    _assert_step1_vs_reference(d, S.Conv3dPlan.WINO3)
     orc64 = O.ACVDiffusionOracle(_f64_state_dict(acv_state_dict))
     _, _, d64, _ = orc64.model_predictions(_volume(g["vol_seed"]).double(), g["x_T"], g["t"])
     e_hip, e_ref = (pred.cpu().double() - d64).abs(), (g["pred"].double() - d64).abs()
@@ -472,9 +553,12 @@ def test_ddim_sample_golden(model, acv_state_dict):
     d = (stack.cpu() - g["stack"]).abs()
     for i in range(1, 6):
         assert float(d[i].median()) < 1e-4, (i, float(d[i].median()))
-    # (step 1 is test_model_predictions_golden's step: two fp32 evaluations, each within 1e-3 px of the float64 one)
-    assert float(d[1].mean()) < 2e-4 and float(d[1].max()) < 2e-3 and float((d[1] > 1e-3).float().mean()) <= 2.5e-3, \
-        (float(d[1].mean()), float(d[1].max()), float((d[1] > 1e-3).float().mean()))
+    # (step 1 is test_model_predictions_golden's step: two fp32 evaluations, each within 1e-3 px of the float64 one;
+    # the same ceilings per routing)
+    _assert_step1_vs_reference(d[1], S.Conv3dPlan.WINO3)
+    with _wino3(False):
+        _, stack_ip = model.ddim_sample(dev(vol), dev(g["used"]), dev(g["x_T"]), noise=NoiseTape(g["tape_seed"]))
+    _assert_step1_vs_reference((stack_ip[1].cpu() - g["stack"][1]).abs(), False)
     rep = _assert_loop_contract(model, acv_state_dict, vol, g["used"], g["x_T"], g["tape_seed"])
     print("ddim_sample fixture:", rep)
     for i, (e_h, e_o) in enumerate(_teacher_forced_vs_fp64(model, acv_state_dict, vol, g["used"], g["x_T"], g["tape_seed"])):

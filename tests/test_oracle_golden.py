@@ -115,7 +115,7 @@ def test_deconv_layer():
     close(O._bn(up, {"b." + k[2:]: v for k, v in sd.items() if k.startswith("1.")}, "b"), g["y"])
 
 
-@pytest.mark.parametrize("tag", ["nopad", "pad", "padw"])
+@pytest.mark.parametrize("tag", ["nopad", "pad", "padw", "padh"])
 def test_attention_block(tag):
     from diffuvolume_amd.acv_ddim import _WindowAttention
     g = load_golden(f"layer_attention_{tag}")
