@@ -18,6 +18,9 @@ KNOBS = {
                           "f16x3 = split-fp16 products (opt-in, not the contract's arithmetic)"),
     "DV_S2PP": ("1", "submodule.Conv3dPlan when a stride-2 plan is built",
                 "0 = the stride-2 3-D layers on the direct kernel instead of the polyphase one (tests)"),
+    "DV_TRAIN_CONV3D": ("hip", "train3d.route() on every training convolution",
+                        "torch = the 3-D convolutions of ACVNet_DDIM training on F.conv3d / F.conv_transpose3d instead of "
+                        "the HIP forward, input-gradient and weight-gradient kernels (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_stereo_ddim.IGEVDiffusionLoop.use_graph at import",

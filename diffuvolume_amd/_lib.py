@@ -124,6 +124,8 @@ SIGNATURES = {
     "dv_geo_lookup_conv1x1_pack_weights_f32": (c_int, [P, P, I, P]),
     "dv_geo_filter_lookup_conv1x1_f32": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "dv_masked_metrics_f32": (c_int, [P, P, P, P, I, I, P]),
+    "dv_conv3d_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I, I]),
+    "dv_conv3d_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
 }
 
 

@@ -13,7 +13,9 @@ What runs where
   * the 56 k-parameter time MLP: PyTorch, once per step.
 The dead pre-DDIM aggregation pass of the reference's eval branch (acv_ddim.py:392-401,
 its result ``pred2`` is never returned) is skipped; outputs are unchanged.
-Training is out of scope: ``forward`` raises in training mode.
+Training (``model.train()``, the reference's :424-482 branch): ``forward`` returns
+``[pred_attention, pred0, pred1, pred2]`` with the 3-D convolutions on the differentiable HIP route of
+``train3d.py`` and everything else on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -26,11 +28,12 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from . import train3d
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, Rank1FilterPlan, ReplicaPlanCache,
                         _dev_f32,
-                        AttentionConcatVolume, build_concat_attention_volume, build_gwc_volume, check_split_overflow,
-                        default_conv_precision, patch_volume, upsample_softmax_regress, window_attention)
+                        AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
+                        check_split_overflow, default_conv_precision, disparity_regression, patch_volume, upsample_softmax_regress, window_attention)
 
 
 def any_split_plan(plans) -> bool:
@@ -193,6 +196,67 @@ class Hourglass(nn.Module):
                                    nn.BatchNorm3d(c))
         self.redir1 = _cb3(c, c, 1, 1, 0)
         self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
+
+    def forward(self, x):
+        """Training path (acv_ddim.py:88-93); eval runs ``_HourglassPlan``."""
+        c1 = _train_cbr(self.conv1[0], x)
+        c2 = _train_cbr(self.conv2[0], c1)
+        c3 = _train_cbr(self.conv3[0], c2)
+        c4 = _train_cbr(self.conv4[0], c3)
+        c4 = _train_window_attention(self.attention_block, c4)
+        c5 = F.relu(self.conv5[1](train3d.conv_transpose3d_module(self.conv5[0], c4)) + _train_cb(self.redir2, c2),
+                    inplace=True)
+        return F.relu(self.conv6[1](train3d.conv_transpose3d_module(self.conv6[0], c5)) + _train_cb(self.redir1, x),
+                      inplace=True)
+
+
+def _train_cb(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """convbn_3d in training: the convolution on the HIP route, BatchNorm3d (batch statistics) in PyTorch."""
+    return seq[1](train3d.conv3d_module(seq[0], x))
+
+
+def _train_cbr(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    return F.relu(_train_cb(seq, x), inplace=True)
+
+
+def _train_pair(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """convbn-ReLU-conv[bn][-ReLU] stacks (dres0 / dres1 / classif*, acv_ddim.py:200-222) in training."""
+    y = _train_cbr(seq[0], x)
+    last = seq[2]
+    y = _train_cb(last, y) if isinstance(last, nn.Sequential) else train3d.conv3d_module(last, y)
+    return F.relu(y, inplace=True) if len(seq) > 3 else y
+
+
+def _train_window_attention(ab: "_WindowAttention", x: torch.Tensor, block: int = 4) -> torch.Tensor:
+    """attention_block.forward (SceneFlow/models/submodule.py:398-429) as differentiable PyTorch: multi-head
+    self-attention inside 4 x 4 x 4 windows, H and W zero-padded up to whole windows.  The reference's padding mask
+    (-1000 between a padded and an unpadded token) only takes effect when H AND W are both padded: with one of
+    them whole, its ``mask[:, -0:]`` slice marks every token (the eval kernel, csrc/window_attn.hip, does the same)."""
+    b, c, d, h0, w0 = x.shape
+    ph, pw = (-h0) % block, (-w0) % block
+    xp = F.pad(x, (0, pw, 0, ph))
+    h, w = h0 + ph, w0 + pw
+    nd, nh, nw = d // block, h // block, w // block
+    nwin, ntok, heads = nd * nh * nw, block ** 3, ab.num_heads
+    ch = c // heads
+    # tokens of one window contiguous: [B, windows, tokens, C], token = (z, y, x) inside the window
+    tok = xp.reshape(b, c, nd, block, nh, block, nw, block).permute(0, 2, 4, 6, 3, 5, 7, 1).reshape(b, nwin, ntok, c)
+    qkv = F.linear(tok, ab.qkv_3d.weight, ab.qkv_3d.bias).reshape(b, nwin, ntok, 3, heads, ch)
+    q, k, v = qkv.permute(3, 0, 1, 4, 2, 5).unbind(0)                  # [B, windows, heads, tokens, ch]
+    logits = (q @ k.transpose(-2, -1)) * ch ** -0.5
+    if ph and pw:
+        rows = torch.arange(h, device=x.device).view(nh, 1, block, 1) >= h0
+        cols = torch.arange(w, device=x.device).view(1, nw, 1, block) >= w0
+        padded = (rows | cols).reshape(nh * nw, 1, block * block)    # [h*w windows, 1, in-plane]
+        padded = padded.expand(nh * nw, block, block * block).reshape(nh * nw, ntok)      # depth repeats the plane
+        padded = padded.repeat(nd, 1)                                                      # [windows, tokens]
+        bias = torch.zeros((nwin, ntok, ntok), dtype=logits.dtype, device=x.device)
+        bias = bias.masked_fill(padded.unsqueeze(2) != padded.unsqueeze(1), -1000.0)
+        logits = logits + bias.unsqueeze(1)
+    y = torch.softmax(logits, dim=-1) @ v                               # [B, windows, heads, tokens, ch]
+    y = y.reshape(b, nd, nh, nw, heads, block, block, block, ch).permute(0, 4, 8, 1, 5, 2, 6, 3, 7)
+    y = y.reshape(b, c, d, h, w)[:, :, :, :h0, :w0]
+    return train3d.conv3d_module(ab.final1x1, y)
 
 
 # --------------------------------------------------------------------------------------
@@ -697,9 +761,69 @@ class ACVNet_DDIM(_HipPlanMixin):
         cr = p.concat_b(p.concat_a(feat_right))
         return build_concat_attention_volume(cl, cr, att, self.maxdisp // 4, lazy=lazy)
 
+    def train_forward(self, left, right, disp, mask_gt=None):
+        """The reference's training branch (acv_ddim.py:372-399, :424-482) -> [pred_attention, pred0, pred1, pred2].
+        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order)."""
+        if not left.is_cuda:
+            raise NotImplementedError("training runs on the MI355X only (model.cuda()); no CPU path")
+        fl = self.feature_extraction(left)["gwc_feature"]
+        fr = self.feature_extraction(right)["gwc_feature"]
+        gwc = build_gwc_volume(fl, fr, self.maxdisp // 4, self.num_groups)
+        gwc = self.patch(gwc)
+        patch = torch.cat((self.patch_l1(gwc[:, :8]), self.patch_l2(gwc[:, 8:24]), self.patch_l3(gwc[:, 24:40])), dim=1)
+        cost_attention = _train_pair(self.dres1_att_, patch)
+        cost_attention = self.dres2_att_(cost_attention)
+        att_weights = _train_pair(self.classif_att_, cost_attention)
+
+        cl = self.concatconv(fl)
+        cr = self.concatconv(fr)
+        concat_volume = build_concat_volume(cl, cr, self.maxdisp // 4)
+        ac_volume = F.softmax(att_weights, dim=2) * concat_volume
+
+        # :384-398 run the aggregation stack once on the un-filtered volume in training mode too; its prediction is
+        # overwritten, but the BatchNorm layers of dres0..dres3 / classif2 update their running statistics on it
+        with torch.no_grad():
+            cost0 = _train_pair(self.dres0, ac_volume)
+            cost0 = _train_pair(self.dres1, cost0) + cost0
+            _train_pair(self.classif2, self.dres3(self.dres2(cost0)))
+            del cost0
+
+        # two-hot x_start (:426-439), the mask_gt form of the training branch
+        x_start = self.encode_disparity(disp.detach().float())
+        if mask_gt is not None:
+            uniform = ((torch.ones((), dtype=torch.float32, device=x_start.device) / (self.maxdisp // 4)) * 2 - 1) * self.scale
+            x_start = torch.where(mask_gt.to(x_start.device).unsqueeze(1) == 0, uniform, x_start.unsqueeze(1)).squeeze(1)
+        t = torch.randint(0, self.num_timesteps, (1,), device=x_start.device).long()
+        noise = torch.randn_like(x_start)
+        with torch.no_grad():                      # `torch.tensor(noisy)` (:449): no gradient reaches time_embedding
+            noisy = (self.sqrt_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * x_start
+                     + self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * noise)
+            noisy = self.time_embedding(noisy, t)
+            noisy = torch.clamp(noisy, min=-1 * self.scale, max=self.scale)
+            noisy = ((noisy / self.scale) + 1) / 2.
+            noisy = noisy.unsqueeze(1).to(torch.float32)
+
+        ac_volume = ac_volume * noisy
+        cost0 = _train_pair(self.dres0, ac_volume)
+        cost0 = _train_pair(self.dres1, cost0) + cost0
+        out1 = self.dres2(cost0)
+        out2 = self.dres3(out1)
+
+        size = [self.maxdisp, left.size()[2], left.size()[3]]
+
+        def regress(cost):
+            cost = torch.squeeze(F.interpolate(cost, size, mode="trilinear"), 1)
+            return disparity_regression(F.softmax(cost, dim=1), self.maxdisp)
+
+        pred_attention = regress(att_weights)
+        pred0 = regress(_train_pair(self.classif0, cost0))
+        pred1 = regress(_train_pair(self.classif1, out1))
+        pred2 = regress(_train_pair(self.classif2, out2))
+        return [pred_attention, pred0, pred1, pred2]
+
     def forward(self, left, right, used, disp, mask_gt=None):
         if self.training:
-            raise NotImplementedError("the MI355X DiffuVolume path is inference-only (model.eval())")
+            return self.train_forward(left, right, disp, mask_gt)
         with torch.no_grad():
             self.prepare(check_weights=True)
             fl = self.feature_extraction(left)["gwc_feature"]

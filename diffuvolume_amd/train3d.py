@@ -1,0 +1,141 @@
+"""Differentiable 3-D convolutions on the HIP kernels (training of ACVNet_DDIM's aggregation stack).
+
+``conv3d(x, w, bias=None, stride=1)`` (cubic k in {1, 3}, pad (k-1)/2, stride 1 | 2) and ``conv_transpose3d(x, w)``
+(k3 s2 p1 op1, bias-free) are ``torch.autograd.Function``s whose three products all run on libdiffuvolume_hip.so:
+  * forward: the inference kernels through ``Conv3dPlan`` / ``Deconv3dPlan`` (no BN folding, no activation);
+  * input gradient: the same forward kernels on the output gradient, with the weights repacked on every call
+        stride-1 3x3x3   conv of g with w.flip(2,3,4).transpose(0,1)   (Winograd routing applies)
+        stride-2 3x3x3   transposed conv of g with w as is              (dims must be even)
+        transposed conv  stride-2 conv of g with w as is                (polyphase / direct)
+        1x1x1            conv of g with w^T
+    (the kernels pad channel counts internally, so 40 -> 32 layers and the 32 -> 1 head need no padding here);
+  * weight gradient: ``dv_conv3d_wgrad_f32`` (csrc/conv3d_wgrad.hip), the transposed form with x and g exchanged.
+BatchNorm and ReLU stay PyTorch.  ``DV_TRAIN_CONV3D=torch`` routes both functions to ``F.conv3d`` /
+``F.conv_transpose3d`` instead (A/B runs, tests).  CPU tensors raise, as everywhere on the hot path."""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan
+
+
+def route() -> str:
+    """'hip' (default) or 'torch' (DV_TRAIN_CONV3D)."""
+    r = os.environ.get("DV_TRAIN_CONV3D", "hip") or "hip"
+    if r not in ("hip", "torch"):
+        raise ValueError(f"DV_TRAIN_CONV3D must be 'hip' or 'torch', got {r!r}")
+    return r
+
+
+def _check(t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+
+
+def conv3d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int, cout: int) -> torch.Tensor:
+    """dW [Cout,Cin,k,k,k] of a cubic convolution (pad (k-1)/2) with input ``x`` and output gradient ``g``."""
+    x, g = x.contiguous(), g.contiguous()
+    b, cin, d, h, w = x.shape
+    lib = _lib.load()
+    n = lib.dv_conv3d_wgrad_workspace_floats(b, cin, d, h, w, cout, k, stride)
+    if n == 0:
+        raise _lib.DiffuVolumeError(f"dv_conv3d_wgrad_f32 does not take k={k} stride={stride}")
+    dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dv_conv3d_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d, h, w,
+                                           cout, k, stride, _lib.stream_ptr()), "dv_conv3d_wgrad_f32")
+    return dw
+
+
+def _plan(w: torch.Tensor, stride: int, bias: Optional[torch.Tensor] = None) -> Conv3dPlan:
+    return Conv3dPlan(w.contiguous(), None, stride=stride, act=ACT_NONE, bias=bias, precision="f32")
+
+
+class Conv3dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        _check(x, "x")
+        _check(weight, "weight")
+        k = weight.shape[2]
+        if tuple(weight.shape[2:]) != (k, k, k) or k not in (1, 3) or stride not in (1, 2) or (k == 1 and stride != 1):
+            raise _lib.DiffuVolumeError(f"unsupported Conv3d: kernel {tuple(weight.shape[2:])}, stride {stride}")
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.has_bias = stride, bias is not None
+        return _plan(weight.detach(), stride, None if bias is None else bias.detach())(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        stride, k = ctx.stride, w.shape[2]
+        g = g.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            if k == 1:
+                dx = _plan(w.detach().transpose(0, 1), 1)(g)
+            elif stride == 1:
+                dx = _plan(w.detach().flip(2, 3, 4).transpose(0, 1), 1)(g)
+            else:
+                if any(n % 2 for n in x.shape[2:]):
+                    raise _lib.DiffuVolumeError(f"stride-2 input gradient needs even dims, got {tuple(x.shape[2:])}")
+                dx = Deconv3dPlan(w.detach().contiguous(), None, act=ACT_NONE)(g)
+        if ctx.needs_input_grad[1]:
+            dw = conv3d_weight_grad(x, g, k, stride, w.shape[0])
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = g.sum(dim=(0, 2, 3, 4))
+        return dx, dw, db, None
+
+
+class ConvTranspose3dFn(torch.autograd.Function):
+    """nn.ConvTranspose3d(k=3, stride=2, padding=1, output_padding=1, bias=False); weight [Cin,Cout,3,3,3]."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        _check(x, "x")
+        _check(weight, "weight")
+        if tuple(weight.shape[2:]) != (3, 3, 3):
+            raise _lib.DiffuVolumeError(f"unsupported ConvTranspose3d kernel {tuple(weight.shape[2:])}")
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        return Deconv3dPlan(weight.detach().contiguous(), None, act=ACT_NONE)(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _plan(w.detach(), 2)(g)
+        if ctx.needs_input_grad[1]:
+            dw = conv3d_weight_grad(g, x, 3, 2, w.shape[0])          # x and g exchanged
+        return dx, dw
+
+
+def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1) -> torch.Tensor:
+    k = weight.shape[2]
+    if route() == "torch":
+        return F.conv3d(x, weight, bias, stride=stride, padding=(k - 1) // 2)
+    return Conv3dFn.apply(x, weight, bias, stride)
+
+
+def conv_transpose3d(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    if route() == "torch":
+        return F.conv_transpose3d(x, weight, None, stride=2, padding=1, output_padding=1)
+    return ConvTranspose3dFn.apply(x, weight)
+
+
+def conv3d_module(m: torch.nn.Conv3d, x: torch.Tensor) -> torch.Tensor:
+    """An nn.Conv3d of the aggregation stack (cubic kernel, padding (k-1)/2) on the differentiable HIP route."""
+    return conv3d(x, m.weight, m.bias, stride=m.stride[0])
+
+
+def conv_transpose3d_module(m: torch.nn.ConvTranspose3d, x: torch.Tensor) -> torch.Tensor:
+    return conv_transpose3d(x, m.weight)

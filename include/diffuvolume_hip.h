@@ -526,6 +526,19 @@ int dv_geo_filter_lookup_conv1x1_f32(const float* geo, const float* corr0, const
                                      float* out, int B, int C, int D, int h, int w, int W2, int radius, int Cout, int act,
                                      dv_stream_t stream);
 
+/* ---- weight gradient of the 3-D convolutions (training) ---------------------
+ * dW[co, ci, t] = sum_{b, o} g[b, co, o] * x[b, ci, stride*o + t - p] for the convolutions of dv_conv3d_f32
+ * (cubic k in {1, 3}, p = (k-1)/2, stride in {1, 2}; k = 1 needs stride 1); x [B,Cin,D,H,W], g [B,Cout,Do,Ho,Wo],
+ * dw [Cout,Cin,k,k,k], all fp32 and contiguous.  Implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32) with the K
+ * dimension (B*Do*Ho*Wo) split over blocks: every split writes its partial into `workspace`
+ * (dv_conv3d_wgrad_workspace_floats floats, at most 48 MB; 0 = unsupported arguments) and a second kernel sums the
+ * splits in a fixed order -- no atomics, the same bits on every launch.
+ * The weight gradient of ConvTranspose3d(k3, s2, p1, op1) with weight [Cin_t,Cout_t,3,3,3] is this call with x and g
+ * exchanged: x = the transposed convolution's output gradient (Cin = Cout_t, D = 2*D_t), g = its input (Cout = Cin_t). */
+size_t dv_conv3d_wgrad_workspace_floats(int B, int Cin, int D, int H, int W, int Cout, int k, int stride);
+int dv_conv3d_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int D, int H,
+                        int W, int Cout, int k, int stride, dv_stream_t stream);
+
 /* ---- metrics (SceneFlow/utils/metrics.py:22-65) -------------------------------
  * Per-image sums over pixels with mask!=0: sums[b] = { n_mask, n_gt_pos, sum|gt-est|,
  * n_D1 (err>3 & err/|gt|>0.05), n_err>1, n_err>2, n_err>3, 0 } as fp64 [B,8].
