@@ -5,13 +5,14 @@ from ._lib import DiffuVolumeError, lib_path, load
 from .submodule import (AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
                         disparity_regression, upsample_softmax_regress)
 from .acv_ddim import ACVNet, ACVNet_DDIM, __models__
-from .loss import model_loss_test, model_loss_train, model_loss_train_attn_only, model_loss_train_freeze_attn
+from .loss import (model_loss_kitti12, model_loss_test, model_loss_train, model_loss_train_attn_only,
+                   model_loss_train_freeze_attn)
 from .pwcnet_ddim import PWCNet, PWCNet_G, PWCNet_GC, PWCNet_ddim
 
 __all__ = ["ACVNet", "ACVNet_DDIM", "PWCNet", "PWCNet_ddim", "__models__", "build_gwc_volume", "build_concat_volume",
            "build_concat_attention_volume", "AttentionConcatVolume", "disparity_regression", "upsample_softmax_regress",
            "DiffuVolumeError", "lib_path", "load", "model_loss_train", "model_loss_train_freeze_attn",
-           "model_loss_train_attn_only", "model_loss_test"]
+           "model_loss_train_attn_only", "model_loss_test", "model_loss_kitti12"]
 # KITTI12/models/__init__.py:5-9: the origin network under both registry names and the DiffuVolume flavour
 __models__ = dict(__models__, **{"gwcnet-g": PWCNet_G, "gwcnet-gc": PWCNet_GC,
                                  "pwc_ddimgc": lambda d: PWCNet_ddim(d, use_concat_volume=True)})

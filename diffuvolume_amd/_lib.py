@@ -126,6 +126,8 @@ SIGNATURES = {
     "dv_masked_metrics_f32": (c_int, [P, P, P, P, I, I, P]),
     "dv_conv3d_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I, I]),
     "dv_conv3d_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "dv_conv2d_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I]),
+    "dv_conv2d_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P]),
 }
 
 

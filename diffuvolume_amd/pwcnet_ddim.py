@@ -15,6 +15,10 @@ The multi-scale 2-D feature CNN runs on the same 2-D kernel; PyTorch keeps the b
 concatenations.
 Differences from the ACV flavour: x_T = randn, 3 steps, fill = cumulative
 q_sample(asd), thresholds dif<1 & unc<1, ensemble [0.9,0,0,0.1], Mish activations.
+Training (``model.train()``, the reference's :643-735 branch): ``forward`` returns
+``[pred0, combine, pred1, pred2, pred3, disp_finetune]`` with the 3-D convolutions on ``train3d.py``, the 2-D
+convolutions of ``refinenet3`` on ``train2d.py`` and everything else (feature CNN, BatchNorm, Mish, warp,
+correlation, ``dispupsample`` in float64) on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -26,12 +30,13 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, train2d, train3d
 from .acv_ddim import ProbVolumeHandle, _LoopStep, _bn_of, _plan_cb3, cosine_beta_schedule
 from .head import DynamicHead
 from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, ReplicaPlanCache, _dev_f32, build_concat_volume,
-                        build_gwc_volume, check_split_overflow, refine_inputs, upsample_softmax_regress)
+                        build_gwc_volume, check_split_overflow, disparity_regression, refine_inputs,
+                        upsample_softmax_regress)
 
 NoiseFn = Callable[[str, Tuple[int, ...], torch.dtype], torch.Tensor]
 
@@ -41,6 +46,28 @@ class Mish(nn.Module):
 
     def forward(self, x):
         return x * torch.tanh(F.softplus(x))
+
+
+def fmish(x):
+    """FMish (KITTI12/models/submodule.py:177-189)."""
+    return x * torch.tanh(F.softplus(x))
+
+
+def _train_seq(seq: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """A Sequential of the training graph: 3-D convolutions on `train3d`, 2-D ones on `train2d` (refinenet3 only),
+    BatchNorm and Mish in PyTorch."""
+    for m in (seq if isinstance(seq, nn.Sequential) else (seq,)):
+        if isinstance(m, nn.Sequential):
+            x = _train_seq(m, x)
+        elif isinstance(m, nn.ConvTranspose3d):
+            x = train3d.conv_transpose3d_module(m, x)
+        elif isinstance(m, nn.Conv3d):
+            x = train3d.conv3d_module(m, x)
+        elif isinstance(m, nn.Conv2d):
+            x = train2d.conv2d_module(m, x)
+        else:
+            x = m(x)
+    return x
 
 
 def _cb2(cin, cout, k, stride, pad, dil):
@@ -223,6 +250,14 @@ class RefineNet(nn.Module, _Stacker):
             x = m(x)
         return disp + x
 
+    def train_forward(self, x, disp):
+        """pwcnet_ddim.py:292-306 in training: every convolution on `train2d`."""
+        x = _train_seq(nn.Sequential(self.conv1, self.conv2, self.conv3, self.conv4), x)
+        for blk in (self.conv5[0], self.conv6[0], self.conv7[0]):        # BasicBlock (submodule.py:192-215)
+            skip = x if blk.downsample is None else _train_seq(blk.downsample, x)
+            x = _train_seq(blk.conv2, _train_seq(blk.conv1, x)) + skip
+        return disp + _train_seq(self.conv8, x)
+
 
 class HourglassUp(nn.Module):
     """Parameters of hourglassup (pwcnet_ddim.py:131-205): fuses the 1/8, 1/16, 1/32 volumes."""
@@ -248,6 +283,15 @@ class HourglassUp(nn.Module):
         self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
         self.redir3 = _cb3(4 * c, 4 * c, 1, 1, 0)
 
+    def forward(self, x, f4, f5, f6):
+        """Training path (pwcnet_ddim.py:181-205); eval runs ``_HourglassUpPlan``."""
+        c2 = _train_seq(self.conv2, _train_seq(self.combine1, torch.cat((_train_seq(self.conv1, x), f4), dim=1)))
+        c4 = _train_seq(self.conv4, _train_seq(self.combine2, torch.cat((_train_seq(self.conv3, c2), f5), dim=1)))
+        c6 = _train_seq(self.conv6, _train_seq(self.combine3, torch.cat((_train_seq(self.conv5, c4), f6), dim=1)))
+        c7 = fmish(_train_seq(self.conv7, c6) + _train_seq(self.redir3, c4))
+        c8 = fmish(_train_seq(self.conv8, c7) + _train_seq(self.redir2, c2))
+        return fmish(_train_seq(self.conv9, c8) + _train_seq(self.redir1, x))
+
 
 class Hourglass(nn.Module):
     """Parameters of the Mish hourglass (pwcnet_ddim.py:208-248): no bottleneck attention."""
@@ -264,6 +308,13 @@ class Hourglass(nn.Module):
                                    nn.BatchNorm3d(c))
         self.redir1 = _cb3(c, c, 1, 1, 0)
         self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
+
+    def forward(self, x):
+        """Training path (pwcnet_ddim.py:235-248); eval runs ``_HourglassPlan``."""
+        c2 = _train_seq(self.conv2, _train_seq(self.conv1, x))
+        c4 = _train_seq(self.conv4, _train_seq(self.conv3, c2))
+        c5 = fmish(_train_seq(self.conv5, c4) + _train_seq(self.redir2, c2))
+        return fmish(_train_seq(self.conv6, c5) + _train_seq(self.redir1, x))
 
 
 # ---- prepared hot-path layers ---------------------------------------------------------------------
@@ -487,6 +538,24 @@ def groupwise_corr_pm(ref: torch.Tensor, tgt: torch.Tensor, maxdisp: int) -> tor
         else:
             out[:, maxdisp] = (ref * tgt).mean(dim=1)
     return out
+
+
+def warp(x: torch.Tensor, disp: torch.Tensor) -> torch.Tensor:
+    """warp (KITTI12/models/submodule.py:137-175) as written there: the grid is normalised by W-1 / H-1 but sampled
+    with grid_sample's default align_corners=False (bilinear, zero padding); the mask is the grid_sample of ones set to
+    0 below 0.999 and to 1 elsewhere (it carries no gradient, every entry is overwritten).  The gradient reaches
+    ``disp`` through the sampling grid."""
+    b, c, h, w = x.shape
+    xx = torch.arange(0, w, device=x.device).view(1, 1, 1, w).expand(b, 1, h, w).to(x.dtype)
+    yy = torch.arange(0, h, device=x.device).view(1, 1, h, 1).expand(b, 1, h, w).to(x.dtype)
+    gx = 2.0 * (xx - disp) / max(w - 1, 1) - 1.0
+    gy = 2.0 * yy / max(h - 1, 1) - 1.0
+    grid = torch.cat((gx, gy), 1).permute(0, 2, 3, 1)
+    out = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+    with torch.no_grad():
+        ones = torch.ones((b, 1, h, w), dtype=x.dtype, device=x.device)       # equal in every channel
+        mask = (F.grid_sample(ones, grid, mode="bilinear", padding_mode="zeros", align_corners=False) >= 0.999).to(x.dtype)
+    return out * mask
 
 
 class _PWCCommon(ReplicaPlanCache):
@@ -865,9 +934,92 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
                                                          _lib.stream_ptr()), "dv_encode_two_hot_f32")
         return x
 
+    def train_forward(self, left, right, disp):
+        """The reference's training branch (pwcnet_ddim.py:604-735) -> [pred0, combine, pred1, pred2, pred3,
+        disp_finetune], each [B,H,W].  ``disp``: the quarter-resolution disparity [B,1,H/4,W/4] (KITTI12/main.py:148-150).
+        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order)."""
+        if not left.is_cuda:
+            raise NotImplementedError("training runs on the MI355X only (model.cuda()); no CPU path")
+        hh, ww = left.shape[-2], left.shape[-1]
+        if hh % 32 or ww % 32:
+            raise _lib.DiffuVolumeError(f"PWCNet_ddim training needs H and W divisible by 32, got {hh}x{ww}: the stride-2 "
+                                        "input gradient of the 3-D stack needs even dims at 1/4, 1/8 and 1/16")
+        fl = self.feature_extraction(left)
+        fr = self.feature_extraction(right)
+        vols = []
+        for i, div in enumerate((4, 8, 16, 32), start=1):
+            v = build_gwc_volume(fl[f"gw{i}"], fr[f"gw{i}"], self.maxdisp // div, self.num_groups)
+            if self.use_concat_volume:
+                cv = build_concat_volume(fl[f"concat_feature{i}"], fr[f"concat_feature{i}"], self.maxdisp // div,
+                                         zero_left=True)
+                v = torch.cat((v, cv), 1)
+            vols.append(v)
+        cost0 = _train_seq(self.dres0, vols[0])
+        cost0 = _train_seq(self.dres1, cost0) + cost0
+        combine = self.combine1(cost0, vols[1], vols[2], vols[3])
+
+        # two-hot disp_volume_final (:644-659), then t, then q_sample's noise
+        x_start = self.encode_disparity(disp.detach().float())
+        t = torch.randint(0, self.num_timesteps, (1,), device=x_start.device).long()
+        noise = torch.randn_like(x_start)
+        with torch.no_grad():                      # `torch.tensor(noisy)` (:667): no gradient reaches time_embedding
+            noisy = (self.sqrt_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * x_start
+                     + self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * noise)
+            noisy = self.time_embedding(noisy, t)
+            noisy = torch.clamp(noisy, min=-1 * self.scale, max=self.scale)
+            noisy = ((noisy / self.scale) + 1) / 2.
+            noisy = noisy.unsqueeze(1).to(torch.float32)
+
+        out1 = self.dres2(combine * noisy)
+        out2 = self.dres3(out1)
+        out3 = self.dres4(out2)
+        size = [self.maxdisp, hh, ww]
+
+        def regress(cost):
+            cost = torch.squeeze(F.interpolate(cost, size, mode="trilinear", align_corners=True), 1)
+            return disparity_regression(F.softmax(cost, dim=1), self.maxdisp)
+
+        pred0 = regress(_train_seq(self.classif0, cost0))
+        pred1 = regress(_train_seq(self.classif1, out1))
+        pred2 = regress(_train_seq(self.classif2, out2))
+        pred3 = regress(_train_seq(self.classif3, out3)).unsqueeze(1)
+        pred_combine = regress(_train_seq(self.classif4, combine))
+
+        # refinement (:711-728)
+        rl, rr = self.refine_features(fl, fr, (hh, ww))
+        rr_warp = warp(rr, pred3)
+        corr = groupwise_corr_pm(rl, rr_warp, 24)
+        refine_in = torch.cat((rl - rr_warp, rl, self._dispupsample_train(pred3), pred3, corr), dim=1)
+        disp_finetune = self.refinenet3.train_forward(refine_in, pred3).squeeze(1)
+        return [pred0, pred_combine, pred1, pred2, pred3.squeeze(1), disp_finetune]
+
+    def _dispupsample_train(self, pred3):
+        """`dispupsample` (1x1 conv 1 -> 32, BatchNorm2d, Mish; pwcnet_ddim.py:722) in training, evaluated in float64.
+
+        With a single input channel the BatchNorm in train mode makes the output independent of the scale of each weight
+        (BN(w * d) = BN(d) * sign(w) up to the eps term), so the weight's gradient -- sum over all pixels of the output
+        gradient times d, behind the BatchNorm backward -- cancels to almost nothing: in float32 it is rounding noise of
+        the size of the result (the reference's own float32 gradient is 2e-3 from float64, and PyTorch's float32
+        reductions make it differ from run to run).  In float64 the cancellation leaves the true value; the layer has 32
+        channels and costs little.  Output, gradients and BatchNorm statistics are stored back in float32."""
+        conv, bn = self.dispupsample[0][0], self.dispupsample[0][1]
+        # a 1x1 conv of one channel is a per-channel scale; BatchNorm2d in train mode as nn.BatchNorm2d computes it
+        # (biased variance to normalise, unbiased into running_var), written out elementwise: no float64 conv / BN path
+        x = pred3.double() * conv.weight.double().view(1, -1, 1, 1)
+        mean = x.mean(dim=(0, 2, 3), keepdim=True)
+        var = (x - mean).square().mean(dim=(0, 2, 3), keepdim=True)
+        y = (x - mean) / torch.sqrt(var + bn.eps) * bn.weight.double().view(1, -1, 1, 1) + bn.bias.double().view(1, -1, 1, 1)
+        with torch.no_grad():                      # what nn.BatchNorm2d.forward does to its buffers in train mode
+            bn.num_batches_tracked.add_(1)
+            factor = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+            n = x.numel() // x.shape[1]
+            bn.running_mean.mul_(1 - factor).add_((factor * mean.reshape(-1)).float())
+            bn.running_var.mul_(1 - factor).add_((factor * var.reshape(-1) * n / max(n - 1, 1)).float())
+        return fmish(y).float()
+
     def forward(self, left, right, used, disp, mask=None):
         if self.training:
-            raise NotImplementedError("the MI355X DiffuVolume path is inference-only (model.eval())")
+            return self.train_forward(left, right, disp)
         with torch.no_grad():
             self.prepare(check_weights=True)
             fl = self.feature_extraction(left)

@@ -539,6 +539,19 @@ size_t dv_conv3d_wgrad_workspace_floats(int B, int Cin, int D, int H, int W, int
 int dv_conv3d_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int D, int H,
                         int W, int Cout, int k, int stride, dv_stream_t stream);
 
+/* ---- training: 2-D convolution weight gradient (csrc/conv2d_wgrad.hip) -------------------------------
+ * The backward of the dilated `convbn` / BasicBlock / conv8 layers of refinenet_version3 (KITTI12/models/
+ * pwcnet_ddim.py:251-306, submodule.py:21-24, :192-215) with respect to the weights:
+ *   dw[co, ci, ky, kx] = sum_{b, y, x} g[b, co, y, x] * x[b, ci, y + (ky-1)*d, x + (kx-1)*d]
+ * (k in {1, 3}, stride 1, padding = dilation d in 1..16; x is zero outside the image); x [B,Cin,H,W], g [B,Cout,H,W],
+ * dw [Cout,Cin,k,k], all fp32 and contiguous.  Implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32) with the K dimension
+ * (B*H*W) split over blocks: every split writes its partial into `workspace` (dv_conv2d_wgrad_workspace_floats floats,
+ * at most 48 MB; 0 = unsupported arguments) and a second kernel sums the splits in a fixed order -- no atomics, the same
+ * bits on every launch. */
+size_t dv_conv2d_wgrad_workspace_floats(int B, int Cin, int H, int W, int Cout, int k, int dilation);
+int dv_conv2d_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int H, int W,
+                        int Cout, int k, int dilation, dv_stream_t stream);
+
 /* ---- metrics (SceneFlow/utils/metrics.py:22-65) -------------------------------
  * Per-image sums over pixels with mask!=0: sums[b] = { n_mask, n_gt_pos, sum|gt-est|,
  * n_D1 (err>3 & err/|gt|>0.05), n_err>1, n_err>2, n_err>3, 0 } as fp64 [B,8].
