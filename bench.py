@@ -2,7 +2,7 @@
 """bench.py -- stereo pairs/s of the DiffuVolume hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sceneflow|kitti12|kitti15] [--batch B] [--height H] [--width W]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-kernel-timer] [--no-cpu-baseline] [--no-extras]]
 
 One "step" = one pass of the hot path (SURVEY 8d "HOT") over one batch of synthetic stereo
 pairs per GPU, inputs already resident in HBM:
@@ -17,9 +17,14 @@ torchrun (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, when those are 
 script itself: `python bench.py --gpus N` starts N workers (before anything touches the GPU), and
 fails if fewer than N devices are visible.  It never silently measures fewer GPUs than asked.
 
-Prints ONE JSON line (rank 0): the driver contract plus `roofline` (dominant kernel: the
-fp32-MFMA Winograd conv of the 32-channel layers, HIP-event timed inside the timed region) and `cpu_baseline`
-(the CPU oracle on a bounded sample of the same workload, rank 0, N=1 only).
+Prints ONE JSON line (rank 0): the driver contract.  A plain run does only what that line needs: set up, W warm-up
+steps, the K timed steps, --dump-outputs, the line.  --full then adds the legs that take runs of their own (each one
+can be left out again with its --no-* switch):
+  - the K steps once more with a HIP-event pair around every kernel (--no-kernel-timer): `roofline` (dominant kernel:
+    the fp32-MFMA Winograd conv of the 32-channel layers), `roofline_kernels` and the per-kernel tables;
+  - `cpu_baseline`, the CPU oracle on a bounded sample of the same workload, and the parity legs against it
+    (--no-cpu-baseline; sceneflow, N=1 only);
+  - `extras`: hipGraph replay, end-to-end and batch-1 latency, BASELINE configs 4 / 5 (--no-extras; sceneflow, N=1 only).
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (see `dump_outputs`) as
 DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
@@ -158,9 +163,13 @@ def parse():
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--ddim-steps", type=int, default=None, help="default: 5 / 3 / 20 (BASELINE configs 2, 4, 5)")
     ap.add_argument("--gru-iters", type=int, default=32, help="kitti15: GRU iterations per DDIM step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the hipGraph, end-to-end and config 4 / 5 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the per-kernel timing pass, the CPU baseline with the parity "
+                         "legs and the side measurements (a plain run does only what the headline figures need)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity legs")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full without the per-kernel timing pass")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the hipGraph, end-to-end and config 4 / 5 side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / float64, "
                          "< 64 MB in all: arrays beyond their share are written as a fixed seeded sample)")
@@ -172,6 +181,8 @@ def parse():
     for k, v in WORKLOADS[a.workload]["defaults"].items():
         if getattr(a, k) is None:
             setattr(a, k, v)
+    if not a.full:                  # a plain run: the timed steps and the line, none of the legs that take runs of their own
+        a.no_cpu_baseline = a.no_kernel_timer = a.no_extras = True
     return a
 
 
@@ -676,10 +687,10 @@ def main_flavour(a, rank, world, device):
            "config": {"workload": what, "global_batch": a.batch * world, "ddim_steps": a.ddim_steps,
                       "parallelism": f"dp{world}"},
            "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
-           "launcher": launcher_label(), "env_overrides": env_overrides(), "epe_px": epe["EPE"],
+           "launcher": launcher_label(), "env_overrides": env_overrides(), "full": a.full, "epe_px": epe["EPE"],
            "epe_note": "random-init weights and synthetic pairs: the number only shows the metric path runs",
            "cpu_baseline": None,
-           "cpu_baseline_note": "timed for the headline workload only (python bench.py); the oracles of configs 4 / 5 are "
+           "cpu_baseline_note": "timed for the headline workload only (python bench.py --full); the oracles of configs 4 / 5 are "
                                 "the checkers of tests/, minutes per pair at these sizes"}
     if dumped is not None:
         out["dump_outputs"] = dumped
@@ -797,8 +808,8 @@ def main():
         if last is not None and rank == 0:
             dumped = dump_outputs(a.dump_outputs, last)
         del last
-        # pass 2 (rank 0's figures are the ones reported): the same K steps again with a HIP-event pair around every
-        # kernel for the roofline / per-kernel numbers; its wall time is reported beside `value`, never as `value`
+        # pass 2 (--full; rank 0's figures are the ones reported): the same K steps again with a HIP-event pair around
+        # every kernel for the roofline / per-kernel numbers; its wall time is reported beside `value`, never as `value`
         timer, dt_events = None, None
         if not a.no_kernel_timer:
             acc = M.MetricAccumulator(device)
@@ -828,6 +839,7 @@ def main():
         "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
         "launcher": launcher_label(),
         "env_overrides": env_overrides(),
+        "full": a.full,
         "epe_px": epe["EPE"],
         "epe_note": "random-init weights and synthetic pairs: the number only shows the metric path runs; dataset EPE "
                     "(0.46 px, README) is unpinned -- no checkpoint or data ship with the reference",

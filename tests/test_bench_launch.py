@@ -175,3 +175,21 @@ def test_dump_outputs_writes_small_arrays_whole_and_samples_large_ones(tmp_path)
     assert info["arrays"]["big"]["sampled_elements"] == sample.size == mod.DUMP_OTHER_BYTES // 4
     assert np.all(np.diff(sample) >= 0) and np.array_equal(sample, big.reshape(-1)[sample.astype(np.int64)].numpy())
     assert np.array_equal(sample, np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_a_plain_run_leaves_every_side_leg_to_full(monkeypatch):
+    """A plain `bench.py` does the timed steps and prints the line; the per-kernel pass, the CPU baseline with its parity
+    legs and the side measurements run only under --full, where each --no-* switch still leaves its leg out."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod4", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    legs = ("no_kernel_timer", "no_cpu_baseline", "no_extras")
+    for argv, full, skipped in ((["--steps", "2"], False, legs),
+                                (["--steps", "2", "--no-extras"], False, legs),
+                                (["--full"], True, ()),
+                                (["--full", "--no-extras"], True, ("no_extras",)),
+                                (["--full", "--no-cpu-baseline", "--no-kernel-timer"], True, ("no_kernel_timer", "no_cpu_baseline"))):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        a = mod.parse()
+        assert a.full is full and {k for k in legs if getattr(a, k)} == set(skipped), argv

@@ -71,7 +71,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["DV_BENCH_OVERSUBSCRIBE"] = "1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2",
-                        "--height", "128", "--width", "256", "--no-cpu-baseline", "--no-extras"],
+                        "--height", "128", "--width", "256", "--full", "--no-cpu-baseline", "--no-extras"],
                        capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -91,7 +91,7 @@ def test_bench_two_ranks_other_workloads(workload, extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["DV_BENCH_OVERSUBSCRIBE"] = "1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "1", "--warmup", "1",
-                        "--batch", "1"] + extra, capture_output=True, text=True, timeout=1000, env=env, cwd=ROOT)
+                        "--batch", "1", "--full"] + extra, capture_output=True, text=True, timeout=1000, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

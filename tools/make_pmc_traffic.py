@@ -55,7 +55,7 @@ stats = glob.glob(str(src / "stats" / "**" / "*kernel_stats.csv"), recursive=Tru
 if stats:
     text = open(stats[0]).read()
     (dst / f"{tag}_kernel_stats.csv").write_text(
-        '"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras   (MI355X)"\n' + text)
+        '"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras   (MI355X)"\n' + text)
 b = src / "bench_under_rocprof.json"
 if b.exists():
     lines = [l for l in b.read_text().splitlines() if l.startswith("{")]

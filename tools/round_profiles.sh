@@ -4,9 +4,9 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=${1:-r06}
 O=gpurun_out
 mkdir -p $O
-python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err;                                   tail -c 200 $O/${T}_bench.err
-python bench.py --workload kitti12 --no-extras > $O/${T}_bench_kitti12.json 2>/dev/null
-python bench.py --workload kitti15 --steps 2 --warmup 1 --no-extras > $O/${T}_bench_kitti15.json 2>/dev/null
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err;                            tail -c 200 $O/${T}_bench.err
+python bench.py --workload kitti12 --full --no-extras > $O/${T}_bench_kitti12.json 2>/dev/null
+python bench.py --workload kitti15 --steps 2 --warmup 1 --full --no-extras > $O/${T}_bench_kitti15.json 2>/dev/null
 bash tools/profile_round.sh $T > $O/${T}_prof.log 2>&1;                                       tail -2 $O/${T}_prof.log
 bash tools/sq_counters_round.sh $T > $O/${T}_sq.log 2>&1;                                     tail -1 $O/${T}_sq.log
 DV_SQ_ARGS="tools/bench_flavours.py --pcw" bash tools/sq_counters_round.sh ${T}_config4 > $O/${T}_sq4.log 2>&1
