@@ -30,7 +30,7 @@ from torch import nn
 from . import _lib
 from . import train3d
 from .head import DynamicHead
-from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, Rank1FilterPlan, ReplicaPlanCache,
+from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
                         AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
                         check_split_overflow, default_conv_precision, disparity_regression, patch_volume, upsample_softmax_regress, window_attention)
@@ -88,7 +88,7 @@ class _ResBlock2dPlan:
         return self.conv2(self.conv1(x), residual=x if self.down is None else self.down(x))
 
 
-class FeatureExtraction(ReplicaPlanCache, nn.Module):
+class FeatureExtraction(PlanCache, nn.Module):
     """2-D feature CNN (acv_ddim.py:14-53): 320-channel 1/4-resolution ``gwc_feature``.  On the GPU (eval) all 55
     convolutions run on the 2-D implicit-GEMM kernel with BN / ReLU / the residual add fused (csrc/conv2d.hip)."""
 
@@ -102,7 +102,6 @@ class FeatureExtraction(ReplicaPlanCache, nn.Module):
         self.layer2 = self._stack(64, 16, 2, 1, 1)
         self.layer3 = self._stack(128, 3, 1, 1, 1)
         self.layer4 = self._stack(128, 3, 1, 1, 2)
-        self._plans = None
 
     def _stack(self, planes, blocks, stride, pad, dil):
         down = None
@@ -113,41 +112,11 @@ class FeatureExtraction(ReplicaPlanCache, nn.Module):
         layers += [_ResBlock2d(planes, planes, 1, None, pad, dil) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        self._replica_clear()
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._plans = None
-        self._replica_clear()
-        return super()._load_from_state_dict(*a, **k)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:
-            self._plans = None
-            self._replica_clear()
-        return super().train(mode)
-
-    def _replicate_for_data_parallel(self):
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return self._mark_replica(replica)
-
-    def prepare(self):
-        version = sum(t._version for t in self.parameters()) + sum(t._version for t in self.buffers())
-        if self._plans is not None and self._plans[2] != version:      # weights overwritten in place since
-            self._plans = None
-        if self._plans is None:
-            dev = self.firstconv[0][0].weight.device
-            self._plans = self._replica_lookup(dev)                      # nn.DataParallel replica: plans parked on the source
-        if self._plans is None:
-            with torch.no_grad():
-                first = [_plan_cb2(self.firstconv[i], ACT_RELU) for i in (0, 2, 4)]
-                stacks = [[_ResBlock2dPlan(b) for b in getattr(self, n)] for n in ("layer1", "layer2", "layer3", "layer4")]
-            self._plans = (first, stacks, version)
-            self._replica_store(dev, self._plans)
-        return self._plans
+    def _build_plans(self, slot):
+        with torch.no_grad():
+            first = [_plan_cb2(self.firstconv[i], ACT_RELU) for i in (0, 2, 4)]
+            stacks = [[_ResBlock2dPlan(b) for b in getattr(self, n)] for n in ("layer1", "layer2", "layer3", "layer4")]
+        return first, stacks
 
     def forward(self, x):
         if not x.is_cuda:
@@ -158,7 +127,7 @@ class FeatureExtraction(ReplicaPlanCache, nn.Module):
             l3 = self.layer3(l2)
             l4 = self.layer4(l3)
             return {"gwc_feature": torch.cat((l2, l3, l4), dim=1)}
-        first, stacks, _ = self.prepare()
+        first, stacks = self.prepare(check_weights=True)
         with torch.no_grad():
             for p in first:
                 x = p(x)
@@ -348,7 +317,6 @@ class _Plans:
             self.sqrt_recip = torch.sqrt(1.0 / ac)
             self.sqrt_recipm1 = torch.sqrt(1.0 / ac - 1)
         self.loop_key = self.loop_steps = None          # per-step constants of the DDIM loop (ACVNet_DDIM._loop_plan)
-        self.weights_version = -1
 
 
 def _volume_arg(volume):
@@ -397,60 +365,15 @@ def cosine_beta_schedule(timesteps: int, s: float = 0.008) -> torch.Tensor:
     return torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999)
 
 
-class _HipPlanMixin(ReplicaPlanCache, nn.Module):
-    """Plan cache shared by the ACV wrappers: BatchNorm folding / weight repacking happens once per weight
-    set and is redone when parameters move, are reloaded (through this module or any wrapper: ``nn.DataParallel(
-    model).load_state_dict`` only reaches ``_load_from_state_dict``) or the train/eval mode really changes."""
-    _plans = None
+class _HipPlanMixin(PlanCache, nn.Module):
+    """The plans of the ACV wrappers (submodule.PlanCache: rebuilt when the weights change)."""
 
-    def _drop_plans(self):
-        self._plans = None
-        self._replica_clear()
-
-    def _apply(self, fn, *args, **kwargs):
-        self._drop_plans()
-        return super()._apply(fn, *args, **kwargs)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._drop_plans()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:          # the reference calls model.eval() on every batch: keep the plans then
-            self._drop_plans()
-        return super().train(mode)
-
-    def _replicate_for_data_parallel(self):
-        """nn.DataParallel copies ``__dict__`` into its per-device replicas: a replica must fold / repack its OWN
-        (broadcast) weights on its own device, not inherit the source module's device-resident plans."""
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return self._mark_replica(replica)
-
-    def _weights_version(self) -> int:
-        """Sum of the in-place version counters of every parameter and buffer: changes whenever a weight is
-        overwritten (``load_state_dict`` on any sub-module, ``p.data.copy_``, an optimizer step)."""
-        return sum(t._version for t in self.parameters()) + sum(t._version for t in self.buffers())
-
-    def prepare(self, check_weights: bool = False) -> _Plans:
-        """Fold BatchNorm and repack weights for the HIP kernels (once per weight set).  The public entry points
-        pass ``check_weights=True``: plans built from weights that were since modified in place are rebuilt."""
-        if check_weights and self._plans is not None and self._plans.weights_version != self._weights_version():
-            self._drop_plans()
-        if self._plans is None:
-            dev = self.dres0[0][0].weight.device
-            if dev.type != "cuda":
-                raise _lib.DiffuVolumeError(
-                    "the ACVNet hot path needs the model on the MI355X (model.cuda()); no CPU fallback")
-            self._plans = self._replica_lookup(dev)          # nn.DataParallel replica: plans parked on the source module
-            if self._plans is not None:
-                self._plans.weights_version = self._weights_version()
-                return self._plans
-            with torch.no_grad(), torch.cuda.device(dev):
-                self._plans = _Plans(self)
-                self._plans.weights_version = self._weights_version()
-            self._replica_store(dev, self._plans)
-        return self._plans
+    def _build_plans(self, slot) -> _Plans:
+        dev = self.dres0[0][0].weight.device
+        if dev.type != "cuda":
+            raise _lib.DiffuVolumeError("the ACVNet hot path needs the model on the MI355X (model.cuda()); no CPU fallback")
+        with torch.no_grad(), torch.cuda.device(dev):
+            return _Plans(self)
 
 
 class ACVNet_DDIM(_HipPlanMixin):
@@ -518,7 +441,6 @@ class ACVNet_DDIM(_HipPlanMixin):
         self.classif1 = self._classifier()
         self.classif2 = self._classifier()
         self._init_weights()
-        self._plans: Optional[_Plans] = None
 
     @staticmethod
     def _classifier():
@@ -866,7 +788,6 @@ class ACVNet(_HipPlanMixin):
         self.classif1 = ACVNet_DDIM._classifier()
         self.classif2 = ACVNet_DDIM._classifier()
         ACVNet_DDIM._init_weights(self)
-        self._plans: Optional[_Plans] = None
 
     attention_logits = ACVNet_DDIM.attention_logits
     attention_concat_volume = ACVNet_DDIM.attention_concat_volume

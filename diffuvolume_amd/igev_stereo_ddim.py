@@ -24,8 +24,8 @@ from torch import nn
 from . import _lib
 from .acv_ddim import cosine_beta_schedule
 from .head import SinusoidalPositionEmbeddings
-from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv2dK4S2Plan, Deconv3dPlan, _dev_f32, build_gwc_volume,
-                        feature_gate, softmax_regress)
+from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv2dK4S2Plan, Deconv3dPlan, PlanCache, _dev_f32, build_gwc_volume,
+                        feature_gate, softmax_regress, weight_key)
 
 
 class DynamicHead180(nn.Module):
@@ -301,7 +301,7 @@ def hip_conv2d(conv: nn.Module, x: torch.Tensor, bn: Optional[nn.BatchNorm2d] = 
     if bn is not None and bn.training:
         raise _lib.DiffuVolumeError("BatchNorm2d in training mode: the HIP front folds running statistics (model.eval())")
     tensors = [conv.weight, conv.bias] + (list(_bn_tuple(bn)) if bn is not None else [])
-    key = (act, tuple((t.data_ptr(), t._version) for t in tensors if t is not None))
+    key = (act, weight_key(t for t in tensors if t is not None))
     hit = _PLAN_CACHE.get(conv)
     if hit is None or hit[0] != key:
         w = conv.weight
@@ -467,7 +467,7 @@ def _run(plans, x):
     return x
 
 
-class hourglass(nn.Module):
+class hourglass(PlanCache, nn.Module):
     """igev_stereo_ddim.py:24-91 (`hourglass(8)`, runs once per pair on the gated gwc volume)."""
 
     def __init__(self, in_channels):
@@ -494,30 +494,15 @@ class hourglass(nn.Module):
         self.feature_att_32 = FeatureAtt(c * 6, 160)
         self.feature_att_up_16 = FeatureAtt(c * 4, 192)
         self.feature_att_up_8 = FeatureAtt(c * 2, 64)
-        self._plans = None
 
-    def prepare(self):
-        if self._plans is None:
-            self._plans = {n: _seq_plans(getattr(self, n)) for n in ("conv1", "conv2", "conv3", "agg_0", "agg_1")}
-            for n in ("conv3_up", "conv2_up", "conv1_up"):
-                self._plans[n] = getattr(self, n).plan()
-        return self._plans
-
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):      # reached also when a parent / wrapper loads the checkpoint
-        self._plans = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):        # nn.DataParallel replicas fold / pack their own weights
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return replica
+    def _build_plans(self, slot):
+        p = {n: _seq_plans(getattr(self, n)) for n in ("conv1", "conv2", "conv3", "agg_0", "agg_1")}
+        for n in ("conv3_up", "conv2_up", "conv1_up"):
+            p[n] = getattr(self, n).plan()
+        return p
 
     def forward(self, x, features):
-        p = self.prepare()
+        p = self.plans()
         conv1 = self.feature_att_8(_run(p["conv1"], x), features[1], inplace=True)
         conv2 = self.feature_att_16(_run(p["conv2"], conv1), features[2], inplace=True)
         conv3 = self.feature_att_32(_run(p["conv3"], conv2), features[3], inplace=True)
@@ -528,7 +513,22 @@ class hourglass(nn.Module):
         return p["conv1_up"](conv1)
 
 
-class IGEVCostVolume(nn.Module):
+def _cost_volume_plans(m):
+    return m.corr_stem.plan(), Conv3dPlan(m.classifier.weight, None, stride=1, act=ACT_NONE)
+
+
+def _cost_volume(m, match_left, match_right, features_left, max_disp):
+    """IGEVStereo_ddim :378-386 on the modules of ``m`` (an IGEVCostVolume or the IGEVStereo_ddim itself): gwc (8 groups)
+    -> corr_stem -> FeatureAtt -> hourglass(8) -> classifier -> softmax + regression."""
+    m.refresh_plans()
+    stem, classifier = m.plans()
+    gwc = stem(build_gwc_volume(match_left, match_right, max_disp // 4, 8))
+    gwc = m.corr_feature_att(gwc, features_left[0], inplace=True)
+    geo = m.cost_agg(gwc, features_left)
+    return geo, softmax_regress(classifier(geo)).unsqueeze(1)          # F.softmax + disparity_regression :382-383
+
+
+class IGEVCostVolume(PlanCache, nn.Module):
     """The volume-side modules of IGEVStereo_ddim (:196-199) and the part of its forward that uses them
     (:377-386).  ``forward(match_left, match_right, features_left)`` returns the geometry encoding volume
     [B,8,D/4,h,w] (what Combined_Geo_Encoding_Volume filters at every GRU iteration) and `init_disp`
@@ -541,34 +541,12 @@ class IGEVCostVolume(nn.Module):
         self.corr_feature_att = FeatureAtt(8, 96)
         self.cost_agg = hourglass(8)
         self.classifier = nn.Conv3d(8, 1, 3, 1, 1, bias=False)
-        self._plans = None
 
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):      # reached also when a parent / wrapper loads the checkpoint
-        self._plans = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):        # nn.DataParallel replicas fold / pack their own weights
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return replica
-
-    def prepare(self):
-        if self._plans is None:
-            self._plans = (self.corr_stem.plan(), Conv3dPlan(self.classifier.weight, None, stride=1, act=ACT_NONE))
-        return self._plans
+    def _build_plans(self, slot):
+        return _cost_volume_plans(self)
 
     def forward(self, match_left, match_right, features_left):
-        stem, classifier = self.prepare()
-        d4 = self.max_disp // 4
-        gwc = stem(build_gwc_volume(match_left, match_right, d4, 8))
-        gwc = self.corr_feature_att(gwc, features_left[0], inplace=True)
-        geo = self.cost_agg(gwc, features_left)
-        cost = classifier(geo)
-        return geo, softmax_regress(cost).unsqueeze(1)          # F.softmax + disparity_regression :382-383
+        return _cost_volume(self, match_left, match_right, features_left, self.max_disp)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -797,7 +775,7 @@ class Feature(nn.Module):
         return [x4, x8, x16, x32]
 
 
-class IGEVStereo_ddim(nn.Module):
+class IGEVStereo_ddim(PlanCache, nn.Module):
     """``IGEVStereo_ddim(args).forward(image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False)
     -> (pred, pred)`` (eval path, igev_stereo_ddim.py:361-427).  ``args``: hidden_dims, n_gru_layers, n_downsample,
     corr_levels, corr_radius, slow_fast_gru, max_disp, mixed_precision.  ``mixed_precision=True`` runs the update block
@@ -880,41 +858,19 @@ class IGEVStereo_ddim(nn.Module):
         self.corr_feature_att = FeatureAtt(8, 96)
         self.cost_agg = hourglass(8)
         self.classifier = nn.Conv3d(8, 1, 3, 1, 1, bias=False)
-        self._plans = None
-        self._spx = None
 
-    # ---- plan cache (same rules as the other wrappers) ----------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._plans = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):
-        r = super()._replicate_for_data_parallel()
-        r._plans = None
-        return r
-
-    def prepare(self):
-        if self._plans is None:
-            self._plans = (self.corr_stem.plan(), Conv3dPlan(self.classifier.weight, None, stride=1, act=ACT_NONE))
-        return self._plans
-
-    def _spx_plans(self):
-        """`spx_2_gru` (transposed conv + BN + LeakyReLU, concat with the 1/2-resolution stem, 3x3 conv + BN + LeakyReLU)
-        and `spx_gru` (biased transposed conv to the 9 convex-upsampling logits) as HIP plans."""
+    def _build_plans(self, slot):
+        """The default slot: corr_stem and classifier of the cost volume.  Slot "spx": `spx_2_gru` (transposed conv + BN +
+        LeakyReLU, concat with the 1/2-resolution stem, 3x3 conv + BN + LeakyReLU) and `spx_gru` (biased transposed conv
+        to the 9 convex-upsampling logits)."""
+        if slot != "spx":
+            return _cost_volume_plans(self)
         c1, c2, head = self.spx_2_gru.conv1, self.spx_2_gru.conv2, self.spx_gru[0]
         bn = lambda m: (m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var) if m.use_bn else ()
-        tensors = (c1.conv.weight, *bn(c1), c2.conv.weight, *bn(c2), head.weight, head.bias)
-        key = tuple((t.data_ptr(), t._version) for t in tensors)        # children loaded / moved / overwritten in place
-        if self._spx is None or self._spx[0] != key:
-            act = lambda m: ACT_LEAKY if m.relu else ACT_NONE
-            self._spx = (key, (Deconv2dK4S2Plan(c1.conv.weight, bn(c1) or None, act=act(c1), eps=c1.bn.eps),
-                               Conv2dPlan(c2.conv.weight, bn(c2) or None, act=act(c2), eps=c2.bn.eps),
-                               Deconv2dK4S2Plan(head.weight, None, bias=head.bias)))
-        return self._spx[1]
+        act = lambda m: ACT_LEAKY if m.relu else ACT_NONE
+        return (Deconv2dK4S2Plan(c1.conv.weight, bn(c1) or None, act=act(c1), eps=c1.bn.eps),
+                Conv2dPlan(c2.conv.weight, bn(c2) or None, act=act(c2), eps=c2.bn.eps),
+                Deconv2dK4S2Plan(head.weight, None, bias=head.bias))
 
     def freeze_bn(self):
         for m in self.modules():
@@ -926,7 +882,7 @@ class IGEVStereo_ddim(nn.Module):
         """:209-217: spx_2_gru / spx_gru (3x3 HIP kernels; the transposed convolutions as four parity convolutions + pixel
         shuffle), then softmax over the 9 taps + context_upsample(disp*4) in one HIP pass.  Returns [B,1,4h,4w]."""
         if mask_feat_4.is_cuda and self.spx_2_gru.concat:
-            up, mix, head = self._spx_plans()
+            up, mix, head = self.plans("spx")
             x = up(mask_feat_4)
             if x.shape != stem_2x.shape:
                 x = F.interpolate(x, size=(stem_2x.shape[-2], stem_2x.shape[-1]), mode="nearest")
@@ -937,12 +893,7 @@ class IGEVStereo_ddim(nn.Module):
 
     def cost_volume(self, match_left, match_right, features_left):
         """:378-386: gwc (8 groups) -> corr_stem -> FeatureAtt -> hourglass(8) -> classifier -> softmax + regression."""
-        stem, classifier = self.prepare()
-        d4 = self.args.max_disp // 4
-        gwc = stem(build_gwc_volume(match_left, match_right, d4, 8))
-        gwc = self.corr_feature_att(gwc, features_left[0], inplace=True)
-        geo = self.cost_agg(gwc, features_left)
-        return geo, softmax_regress(classifier(geo)).unsqueeze(1)
+        return _cost_volume(self, match_left, match_right, features_left, self.args.max_disp)
 
     def _loop(self):
         return IGEVDiffusionLoop(self.time_embedding, self.update_block, self.upsample_disp,
@@ -952,12 +903,14 @@ class IGEVStereo_ddim(nn.Module):
 
     @torch.no_grad()
     def model_predictions(self, coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, noise, t, stem_2x):
+        self.refresh_plans()
         return self._loop().model_predictions(coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, noise,
                                               t, stem_2x)
 
     @torch.no_grad()
     def ddim_sample(self, coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, used, asd, stem_2x,
                     noise=None, generator=None):
+        self.refresh_plans()
         return self._loop().ddim_sample(coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, used, asd,
                                         stem_2x, noise=noise, generator=generator)
 
@@ -1000,6 +953,7 @@ class IGEVStereo_ddim(nn.Module):
     def forward(self, image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False, noise=None):
         if self.training:
             raise NotImplementedError("the MI355X DiffuVolume path is inference-only (model.eval())")
+        self.refresh_plans()
         with torch.no_grad():
             _, stem_2x, init_disp, net_list, inp_list, geo_fn = self._front(image1, image2)
             x0 = self.encode_disparity(flow_gt)

@@ -34,7 +34,7 @@ from . import _lib, train2d, train3d
 from .acv_ddim import ProbVolumeHandle, _LoopStep, _bn_of, _plan_cb3, cosine_beta_schedule
 from .head import DynamicHead
 from .profiling import timed
-from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, ReplicaPlanCache, _dev_f32, build_concat_volume,
+from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, disparity_regression, refine_inputs,
                         upsample_softmax_regress)
 
@@ -110,7 +110,7 @@ def _head2d(cin, mid, cout):
     return nn.Sequential(_cb2(cin, mid, 3, 1, 1, 1), Mish(), nn.Conv2d(mid, cout, 1, bias=False))
 
 
-class FeatureExtraction(ReplicaPlanCache, nn.Module, _Stacker):
+class FeatureExtraction(PlanCache, nn.Module, _Stacker):
     """Multi-scale 2-D feature CNN (pwcnet_ddim.py:12-128): gw1..gw4 at 1/4..1/32, concat features,
     refinement feature.  On the GPU (eval) every convolution runs on the 2-D HIP kernel."""
 
@@ -139,57 +139,24 @@ class FeatureExtraction(ReplicaPlanCache, nn.Module, _Stacker):
             self.concat4 = _head2d(512, 128, concat_feature_channel)
 
     # ---- HIP plans (csrc/conv2d.hip: BN / Mish / residual fused), rebuilt when the parameters change ----
-    _plans = None
-
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        self._replica_clear()
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._plans = None
-        self._replica_clear()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):        # nn.DataParallel replicas: plans parked on the source, per device
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return self._mark_replica(replica)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:
-            self._plans = None
-            self._replica_clear()
-        return super().train(mode)
-
-    def prepare(self):
-        version = sum(t._version for t in self.parameters()) + sum(t._version for t in self.buffers())
-        if self._plans is not None and self._plans.get("version") != version:      # weights overwritten in place since
-            self._plans = None
-        if self._plans is None:
-            dev = self.firstconv[0][0].weight.device
-            self._plans = self._replica_lookup(dev)
-        if self._plans is None:
-            def head(seq):          # convbn + Mish + Conv2d 1x1
-                return (_plan_cb2(seq[0], ACT_MISH), Conv2dPlan(seq[2].weight, None, act=ACT_NONE))
-            with torch.no_grad():
-                p = {"first": [_plan_cb2(self.firstconv[i], ACT_MISH) for i in (0, 2, 4)]}
-                for n in ("layer1", "layer2", "layer3", "layer4", "layer5", "layer7", "layer9"):
-                    p[n] = [_Block2dPlan(b) for b in getattr(self, n)]
-                for n in ("gw2", "gw3", "gw4", "layer11") + (("lastconv", "concat2", "concat3", "concat4") if self.concat_feature else ()):
-                    p[n] = head(getattr(self, n))
-                p["refine"] = (_plan_cb2(self.layer_refine[0], ACT_MISH), _plan_cb2(self.layer_refine[2], ACT_MISH))
-            p["version"] = version
-            self._plans = p
-            self._replica_store(dev, p)
-        return self._plans
+    def _build_plans(self, slot):
+        def head(seq):          # convbn + Mish + Conv2d 1x1
+            return (_plan_cb2(seq[0], ACT_MISH), Conv2dPlan(seq[2].weight, None, act=ACT_NONE))
+        with torch.no_grad():
+            p = {"first": [_plan_cb2(self.firstconv[i], ACT_MISH) for i in (0, 2, 4)]}
+            for n in ("layer1", "layer2", "layer3", "layer4", "layer5", "layer7", "layer9"):
+                p[n] = [_Block2dPlan(b) for b in getattr(self, n)]
+            for n in ("gw2", "gw3", "gw4", "layer11") + (("lastconv", "concat2", "concat3", "concat4") if self.concat_feature else ()):
+                p[n] = head(getattr(self, n))
+            p["refine"] = (_plan_cb2(self.layer_refine[0], ACT_MISH), _plan_cb2(self.layer_refine[2], ACT_MISH))
+        return p
 
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.DiffuVolumeError(f"input is on {x.device}: the feature CNN runs on the MI355X (no CPU fallback)")
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             return self._forward_modules(x)
-        p = self.prepare()
+        p = self.prepare(check_weights=True)
         def run(plans, t):
             for q in plans:
                 t = q(t)
@@ -522,6 +489,7 @@ class _Plans:
             self.alphas_cumprod = ac
             self.sqrt_ac, self.sqrt_1mac = torch.sqrt(ac), torch.sqrt(1.0 - ac)
             self.sqrt_recip, self.sqrt_recipm1 = torch.sqrt(1.0 / ac), torch.sqrt(1.0 / ac - 1)
+        self.loop_key = self.loop_steps = None          # per-step constants of the DDIM loop (PWCNet_ddim._loop_plan)
 
 
 def groupwise_corr_pm(ref: torch.Tensor, tgt: torch.Tensor, maxdisp: int) -> torch.Tensor:
@@ -558,52 +526,16 @@ def warp(x: torch.Tensor, disp: torch.Tensor) -> torch.Tensor:
     return out * mask
 
 
-class _PWCCommon(ReplicaPlanCache):
+class _PWCCommon(PlanCache):
     """What the origin network (`PWCNet`, pwcnet.py:310-507) and `PWCNet_ddim` share: the plan cache, the fused
     multi-scale volume and the 2-D refinement of a regressed disparity."""
 
-    # ---- plan cache ---------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        self._replica_clear()
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):      # reached however the checkpoint arrives (wrapper or direct)
-        self._plans = None
-        self._replica_clear()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):        # nn.DataParallel replicas: plans parked on the source, per device
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = None
-        return self._mark_replica(replica)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:
-            self._plans = None
-            self._replica_clear()
-        return super().train(mode)
-
-    def _weights_version(self) -> int:
-        return sum(t._version for t in self.parameters()) + sum(t._version for t in self.buffers())
-
-    def prepare(self, check_weights: bool = False) -> _Plans:
-        if check_weights and self._plans is not None and self._plans.weights_version != self._weights_version():
-            self._plans = None
-        if self._plans is None:
-            dev = self.dres0[0][0].weight.device
-            if dev.type != "cuda":
-                raise _lib.DiffuVolumeError("PWCNet_ddim hot path needs the model on the MI355X; no CPU fallback")
-            self._plans = self._replica_lookup(dev)          # nn.DataParallel replica: plans parked on the source module
-            if self._plans is not None:
-                self._plans.weights_version = self._weights_version()
-                return self._plans
-            with torch.no_grad(), torch.cuda.device(dev):
-                self._plans = _Plans(self)
-                self._plans.weights_version = self._weights_version()
-                self._plans.loop_key = self._plans.loop_steps = None
-            self._replica_store(dev, self._plans)
-        return self._plans
+    def _build_plans(self, slot) -> _Plans:
+        dev = self.dres0[0][0].weight.device
+        if dev.type != "cuda":
+            raise _lib.DiffuVolumeError("PWCNet_ddim hot path needs the model on the MI355X; no CPU fallback")
+        with torch.no_grad(), torch.cuda.device(dev):
+            return _Plans(self)
 
     @torch.no_grad()
     def fused_volume(self, fl, fr):
@@ -648,7 +580,6 @@ class _PWCCommon(ReplicaPlanCache):
                 m.bias.data.zero_()
             elif isinstance(m, nn.Linear):
                 m.bias.data.zero_()
-        self._plans: Optional[_Plans] = None
 
     @staticmethod
     def refine_features(features_left, features_right, size):

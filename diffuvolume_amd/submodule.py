@@ -12,6 +12,7 @@ runs on the MI355X or raises.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import os
 from typing import Optional, Tuple
 
@@ -494,39 +495,90 @@ class Conv3dPlan:
         return out
 
 
-class ReplicaPlanCache:
-    """Per-device plan cache for ``nn.DataParallel`` (SceneFlow/test_sceneflow_ddim.py:54-61, KITTI12/test.py): the
-    wrapper re-creates its replicas on EVERY forward, so a replica that folded BatchNorm / repacked weights for itself
-    would redo that work for every plan-holding module on every device and call.  Replicas keep a pointer to the module
-    they were copied from and park their plans there, keyed by device and valid for one weight version of the SOURCE
-    (the replicas' own weights are re-broadcast from it each time).  Mixed into the plan-holding modules."""
+def weight_key(tensors) -> tuple:
+    """Identity of a weight set: (storage address, in-place version) of every tensor -- a weight replaced through
+    ``param.data = ...`` changes the address, an in-place write (``copy_``, an optimizer step) the version."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
 
-    def _replica_source(self):
-        return self.__dict__.get("_plan_source")
 
-    def _mark_replica(self, replica):
+class PlanCache:
+    """Mixed into every nn.Module that holds HIP plans (weights repacked for a kernel, BatchNorm folded in).  The module
+    defines ``_build_plans(slot)``; ``plans(slot)`` builds a named slot once and keeps it until the weights change:
+
+    - ``.to()`` / ``.cuda()``, ``load_state_dict`` (through this module or any parent or wrapper: ``nn.DataParallel(
+      model).load_state_dict`` only reaches ``_load_from_state_dict``) and a real train/eval toggle drop the plans;
+    - an in-place write or a ``.data`` swap fires no hook: ``refresh_plans()``, called at the public entry points (never
+      inside a loop), compares the weight key recorded at build time with the current one and drops the plans of the
+      whole subtree when they differ;
+    - ``nn.DataParallel`` re-creates its replicas on EVERY forward (SceneFlow/test_sceneflow_ddim.py:54-61, KITTI12/
+      test.py), so a replica parks the plans it builds on the module it was copied from, keyed by device and slot and
+      valid for one weight key of that SOURCE (the replicas' own weights are re-broadcast from it each time)."""
+
+    @property
+    def _plans(self):
+        """The default slot's plans, None until they are built."""
+        return self.__dict__.get("_plan_slots", {}).get(None)
+
+    def _weight_key(self) -> tuple:
+        return weight_key(itertools.chain(self.parameters(), self.buffers()))
+
+    def _drop_plans(self):
+        for name in ("_plan_slots", "_plan_key", "_replica_plans"):
+            self.__dict__.pop(name, None)
+
+    def plans(self, slot=None):
+        slots = self.__dict__.setdefault("_plan_slots", {})
+        p = slots.get(slot)
+        if p is None:
+            src = self.__dict__.get("_plan_source")
+            if src is not None:
+                # a replica holds its weights as plain attributes (not parameters); nn.DataParallel runs each replica
+                # under its own device, so that is the device its plans are built on
+                where, src_key = (torch.cuda.current_device(), slot), src._weight_key()
+                parked = src.__dict__.setdefault("_replica_plans", {})
+                p = parked[where][1] if where in parked and parked[where][0] == src_key else None
+            if p is None:
+                p = self._build_plans(slot)
+                if src is not None:
+                    parked[where] = (src_key, p)
+            if "_plan_key" not in self.__dict__:
+                self.__dict__["_plan_key"] = self._weight_key()
+            slots[slot] = p
+        return p
+
+    def refresh_plans(self):
+        """Drop every plan in this module's subtree if a weight was written in place or swapped since they were built."""
+        key = self._weight_key()
+        if self.__dict__.get("_plan_key") != key:
+            for m in self.modules():
+                if isinstance(m, PlanCache):
+                    m._drop_plans()
+            self.__dict__["_plan_key"] = key
+
+    def prepare(self, check_weights: bool = False):
+        """The default slot's plans; ``check_weights=True`` refreshes them first (what the public entry points do)."""
+        if check_weights:
+            self.refresh_plans()
+        return self.plans()
+
+    def _apply(self, fn, *args, **kwargs):
+        self._drop_plans()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._drop_plans()
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def train(self, mode: bool = True):
+        if mode != self.training:          # the reference calls model.eval() on every batch: keep the plans then
+            self._drop_plans()
+        return super().train(mode)
+
+    def _replicate_for_data_parallel(self):
+        replica = super()._replicate_for_data_parallel()      # a shallow copy of __dict__: the cache must not be shared
+        replica._drop_plans()
         replica.__dict__["_plan_source"] = self.__dict__.get("_plan_source") or self
         return replica
-
-    def _source_version(self, src):
-        """Identity of the source's weight set: (storage address, in-place version) of every parameter and buffer -- a
-        weight replaced through ``param.data = ...`` changes the address, an in-place write the version."""
-        return tuple((t.data_ptr(), t._version) for t in list(src.parameters()) + list(src.buffers()))
-
-    def _replica_lookup(self, device):
-        src = self._replica_source()
-        if src is None:
-            return None
-        hit = src.__dict__.setdefault("_replica_plans", {}).get(str(device))
-        return hit[1] if hit is not None and hit[0] == self._source_version(src) else None
-
-    def _replica_store(self, device, plans):
-        src = self._replica_source()
-        if src is not None:
-            src.__dict__.setdefault("_replica_plans", {})[str(device)] = (self._source_version(src), plans)
-
-    def _replica_clear(self):
-        self.__dict__.pop("_replica_plans", None)
 
 
 class PointwiseExpandPlan:

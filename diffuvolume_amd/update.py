@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan
+from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan, PlanCache
 
 
 def autocast_f16() -> bool:
@@ -38,37 +38,12 @@ def autocast_f16() -> bool:
     return True
 
 
-class _Planned(nn.Module):
-    """Plans (packed weights on the device) are rebuilt after .to() / load_state_dict(); the fp16-autocast plans
-    (``plans16``) are built lazily next to the fp32 ones and dropped by the same hooks."""
+class _Planned(PlanCache, nn.Module):
+    """Two plan slots (submodule.PlanCache): the fp32 plans (``plans()``) and the fp16-autocast ones (``plans("f16")``),
+    each built lazily by the module's ``_build`` / ``_build16``."""
 
-    def __init__(self):
-        super().__init__()
-        self._plans = None
-        self._plans16 = None
-
-    def _apply(self, fn, *a, **k):
-        self._plans = self._plans16 = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):      # runs for every sub-module, also when a parent is loaded
-        self._plans = self._plans16 = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _replicate_for_data_parallel(self):        # nn.DataParallel replicas fold / pack their own weights
-        replica = super()._replicate_for_data_parallel()
-        replica._plans = replica._plans16 = None
-        return replica
-
-    def plans(self):
-        if self._plans is None:
-            self._plans = self._build()
-        return self._plans
-
-    def plans16(self):
-        if self._plans16 is None:
-            self._plans16 = self._build16()
-        return self._plans16
+    def _build_plans(self, slot):
+        return self._build16() if slot == "f16" else self._build()
 
 
 def _plan(conv: nn.Conv2d, act: int) -> Conv2dPlan:
@@ -99,7 +74,7 @@ class DispHead(_Planned):
         return _plan16(self.conv1, ACT_RELU), _plan16(self.conv2, ACT_NONE)
 
     def forward(self, x):
-        c1, c2 = self.plans16() if autocast_f16() else self.plans()
+        c1, c2 = self.plans("f16") if autocast_f16() else self.plans()
         return c2(c1(_f32(x)))
 
 
@@ -127,7 +102,7 @@ class ConvGRU(_Planned):
     def forward(self, h, cz, cr, cq, *x_list):
         if autocast_f16():
             # (the fp16 plans round z, r*h and the blend (1-z)*h + z*q at the reference's points; see csrc/conv2d_f16.hip)
-            pzr, pq = self.plans16()
+            pzr, pq = self.plans("f16")
             h, cz, cr, cq = _f32(h), _f32(cz), _f32(cr), _f32(cq)
             x_list = tuple(_f32(t) for t in x_list)
         else:
@@ -203,7 +178,7 @@ class BasicMotionEncoder(_Planned):
     def _features16(self, disp, corr):
         """features() under fp16 autocast: convc1 on the materialised lookup (the fused lookup + 1x1 of geo_lookup.hip
         is the fp32 path's), every convolution on its fp16 plan; channel 127 = the float32 disp, unrounded."""
-        p = self.plans16()
+        p = self.plans("f16")
         from .geometry_ddim import GeoLookupRequest
         if isinstance(corr, GeoLookupRequest):
             corr = corr.materialize()
@@ -357,5 +332,5 @@ class BasicMultiUpdateBlock(_Planned):
             if not update:
                 return net
             delta_disp = self.disp_head(net[0])
-            mask_feat_4 = (self.plans16() if mixed else self.plans())(net[0]) if mask else None
+            mask_feat_4 = (self.plans("f16") if mixed else self.plans())(net[0]) if mask else None
         return net, mask_feat_4, delta_disp

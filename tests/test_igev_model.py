@@ -299,3 +299,27 @@ def test_gru_iterations_as_a_hipgraph_give_the_eager_bits():
     finally:
         IGEVDiffusionLoop.use_graph = old
     assert torch.equal(outs[False][0], outs[True][0]) and torch.equal(outs[True][0], outs[True][1])
+
+
+@pytest.mark.gpu
+def test_weights_written_in_place_rebuild_the_plans():
+    """An update-block conv weight and a BatchNorm statistic of hourglass(8) overwritten in place between two forwards
+    (no hook fires): the next forward folds / packs the new values, bit for bit what a model loaded with them gives."""
+    m = build()
+    m.load_state_dict(synth_state_dict(m.state_dict(), seed=3, scale={"update_block.disp_head.conv2.weight": 0.05,
+                                                                      "update_block.disp_head.conv2.bias": 0.0}), strict=True)
+    m = m.to(DEV).eval()
+    ins = [t.to(DEV) for t in golden_inputs(11)]
+
+    def run(model):
+        return model(*ins, iters=3, test_mode=True, noise=NoiseTape(9))[0].clone()
+
+    before = run(m)
+    with torch.no_grad():
+        m.update_block.gru04.convq.weight.mul_(1.5)
+        m.cost_agg.conv1[0].bn.running_var.mul_(2.0)
+    after = run(m)
+    fresh = build()
+    fresh.load_state_dict(m.state_dict(), strict=True)
+    assert not torch.equal(after, before)
+    assert torch.equal(after, run(fresh.to(DEV).eval()))
