@@ -21,8 +21,9 @@ KNOBS = {
     "DV_TRAIN_CONV3D": ("hip", "train3d.route() on every training convolution",
                         "torch = the 3-D convolutions of ACVNet_DDIM training on F.conv3d / F.conv_transpose3d instead of "
                         "the HIP forward, input-gradient and weight-gradient kernels (A/B runs, tests)"),
-    "DV_TRAIN_CONV2D": ("hip", "train2d.route() on every training convolution of refinenet3",
-                        "torch = the 2-D convolutions of PWCNet_ddim's refinement network in training on F.conv2d instead of "
+    "DV_TRAIN_CONV2D": ("hip", "train2d.route() on every training convolution of refinenet3 and of IGEV's update block",
+                        "torch = the 2-D convolutions of PWCNet_ddim's refinement network and the convolutions and ConvGRU gate "
+                        "arithmetic of IGEV's update block in training on F.conv2d / torch expressions instead of "
                         "the HIP forward, input-gradient and weight-gradient kernels (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),

@@ -177,3 +177,49 @@ class StubMobileNetV2(__import__("torch").nn.Module):
         self.blocks = nn.Sequential(_stub_stage(32, 16, 1), _stub_stage(16, 24, 2), _stub_stage(24, 32, 2),
                                     _stub_stage(32, 64, 2), _stub_stage(64, 96, 1), _stub_stage(96, 160, 2),
                                     _stub_stage(160, 320, 1))
+
+
+# ---- the recurrent update block as a training workload (tools/make_golden_update_train.py, tests, tools/bench_update_train.py)
+
+UPDATE_TRAIN_ARGS = dict(corr_levels=2, corr_radius=4, n_gru_layers=3, n_downsample=2)
+UPDATE_TRAIN_HIDDEN = (128, 128, 128)
+
+
+def update_train_inputs(seed: int, b: int, h: int, w: int, iters: int, dtype=torch.float32, device="cpu"):
+    """Seeded inputs of an unrolled training loop of IGEV's update block at a 1/4 plane of h x w: hidden states ``net``
+    (tanh of noise) and context terms ``inp`` (relu of noise) at the three scales -- leaves that require grad --, one
+    correlation tensor per iteration (162 channels), the starting disparity, a ground truth and the weights ``m`` of the
+    loss's mask-feature term."""
+    def rnd(key, *shape):
+        return torch.randn(*shape, generator=_gen(seed, key)).to(device=device, dtype=dtype)
+    planes = [(h, w)]
+    for _ in range(2):
+        planes.append(((planes[-1][0] - 1) // 2 + 1, (planes[-1][1] - 1) // 2 + 1))
+    cor_planes = UPDATE_TRAIN_ARGS["corr_levels"] * (2 * UPDATE_TRAIN_ARGS["corr_radius"] + 1) * 9
+    net = [torch.tanh(rnd(f"net{i}", b, UPDATE_TRAIN_HIDDEN[2 - i], *p)).requires_grad_(True) for i, p in enumerate(planes)]
+    inp = [[torch.relu(rnd(f"inp{i}{j}", b, UPDATE_TRAIN_HIDDEN[2 - i], *p)).requires_grad_(True) for j in range(3)]
+           for i, p in enumerate(planes)]
+    return dict(net=net, inp=inp, corr=[rnd(f"corr{t}", b, cor_planes, h, w) for t in range(iters)],
+                disp=rnd("disp", b, 1, h, w).abs() * 4, gt=rnd("gt", b, 1, h, w).abs() * 4 + 1,
+                m=rnd("m", b, 32, h, w))
+
+
+def update_train_loop(block, x, slow_fast: bool = False):
+    """The reference's training loop around the update block (KITTI15/core/igev_stereo_ddim.py:441-457: the disparity
+    is detached before every call, the hidden states never) with a loss shaped like sequence_loss at 1/4 resolution:
+    sum_i 0.9^(T-1-i) mean|disp_i - gt| + 0.1 mean(mask_feat_i * m).  Returns (loss, per-iteration disparities,
+    per-iteration mask features, final hidden states)."""
+    net, disp = list(x["net"]), x["disp"]
+    iters = len(x["corr"])
+    loss, disps, masks = 0.0, [], []
+    for i in range(iters):
+        disp = disp.detach()
+        if slow_fast:
+            net = block(net, x["inp"], iter16=True, iter08=False, iter04=False, update=False)
+            net = block(net, x["inp"], iter16=True, iter08=True, iter04=False, update=False)
+        net, mask_feat, delta = block(net, x["inp"], x["corr"][i], disp, iter16=True, iter08=True)
+        disp = disp + delta
+        loss = loss + 0.9 ** (iters - 1 - i) * (disp - x["gt"]).abs().mean() + 0.1 * (mask_feat * x["m"]).mean()
+        disps.append(disp)
+        masks.append(mask_feat)
+    return loss, disps, masks, net

@@ -11,8 +11,16 @@
     dilation 1) runs on ``dv_conv2d_1in_f32``, the direct kernel for single-channel inputs;
   * weight gradient: ``dv_conv2d_wgrad_f32`` (csrc/conv2d_wgrad.hip); bias gradient ``g.sum((0, 2, 3))``.
 BatchNorm and Mish stay PyTorch.  ``DV_TRAIN_CONV2D=torch`` routes the function to ``F.conv2d`` instead (A/B runs,
-tests).  CPU tensors raise, as everywhere on the hot path.  Only ``refinenet3`` uses this route; every other 2-D
-convolution of the training graphs keeps PyTorch autograd."""
+tests).  CPU tensors raise, as everywhere on the hot path.  ``refinenet3`` uses this route.
+
+IGEV's recurrent update block (``update.BasicMultiUpdateBlock`` in train mode) uses the second half of this module:
+``TrainConvPlan`` / ``conv_cat`` (a biased 3x3 / 1x1 convolution over a virtual channel concatenation with its
+activation fused), ``GRUTrainPlan`` / ``conv_gru`` (one ``ConvGRUFn`` per ConvGRU call) and ``conv_1in_relu`` (the 7x7
+single-input-channel ``convd1``).  Their weight gradients run
+on ``dv_conv2d_wgrad_cat_f32`` (csrc/conv2d_wgrad_cat.hip) over the un-materialised concatenation; their input gradients
+are ONE forward launch on the output gradient with the flipped / transposed weights, cut into channel views per
+source; the flipped weights are packed once per plan (the module's ``plans("train")`` slot, dropped with the weight
+key), not per call.  Every other 2-D convolution of the training graphs keeps PyTorch autograd."""
 from __future__ import annotations
 
 import os
@@ -22,7 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .submodule import ACT_NONE, Conv2dPlan
+from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan
 from .train3d import _check
 
 
@@ -108,3 +116,275 @@ def conv2d_module(m: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     if m.stride != (1, 1) or m.kernel_size != (k, k) or m.padding != ((d, d) if k == 3 else (0, 0)) or m.groups != 1:
         raise _lib.DiffuVolumeError(f"conv2d_module: stride 1 and padding = dilation only, got {m}")
     return conv2d(x, m.weight, m.bias, dilation=d)
+
+
+# ---- IGEV's update block: convolutions over a virtual concatenation, ConvGRU ----------------------------------------
+
+def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int) -> torch.Tensor:
+    """dW [Cout, sum(c_i), k, k] of a stride-1, dilation-1 convolution (k 3: padding 1) whose input is the channel
+    concatenation of ``sources`` (1..4 tensors, never materialised) and whose output gradient is ``g``."""
+    import ctypes
+    sources = [t.contiguous() for t in sources]
+    g = g.contiguous()
+    b, cout, h, w = g.shape
+    if not 1 <= len(sources) <= 4 or any(t.shape[0] != b or tuple(t.shape[2:]) != (h, w) for t in sources):
+        raise _lib.DiffuVolumeError("conv2d_cat_weight_grad: 1..4 sources with the batch and plane of the gradient")
+    for t in (*sources, g):
+        _check(t, "conv2d_cat_weight_grad operand")
+    ptrs = (ctypes.c_void_p * len(sources))(*[t.data_ptr() for t in sources])
+    chans = (ctypes.c_int * len(sources))(*[t.shape[1] for t in sources])
+    lib = _lib.load()
+    n = lib.dv_conv2d_wgrad_cat_workspace_floats(chans, len(sources), b, h, w, cout, k)
+    if n == 0:
+        raise _lib.DiffuVolumeError(f"dv_conv2d_wgrad_cat_f32 does not take k={k}, channels {list(chans)}, Cout {cout}")
+    dw = torch.empty((cout, sum(chans), k, k), dtype=torch.float32, device=g.device)
+    ws = torch.empty(n, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        _lib.check(lib.dv_conv2d_wgrad_cat_f32(ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h,
+                                               w, cout, k, _lib.stream_ptr()), "dv_conv2d_wgrad_cat_f32")
+    return dw
+
+
+class _InputGradPlan:
+    """The input gradient of a stride-1, dilation-1 convolution as a forward launch: the weights flipped and transposed
+    ([Cin, Cout, k, k]) and packed ONCE.  ``weights``: one tensor, or several whose outputs are concatenated (ConvGRU's
+    z | r pair: the gradient then arrives as one tensor per convolution, read as a virtual concatenation).  A
+    single-channel gradient (DispHead.conv2, 256 -> 1) runs on ``dv_conv2d_1in_f32``."""
+
+    def __init__(self, weights):
+        w = torch.cat([t.detach() for t in weights], dim=0) if len(weights) > 1 else weights[0].detach()
+        self.k = int(w.shape[2])
+        wt = (w.transpose(0, 1) if self.k == 1 else w.flip(2, 3).transpose(0, 1)).contiguous()
+        self.cin = int(wt.shape[0])
+        self.one_in = w.shape[0] == 1 and self.k == 3
+        self.wt = wt if self.one_in else None
+        self.plan = None if self.one_in else Conv2dPlan(wt, None, dilation=1, act=ACT_NONE)
+
+    def __call__(self, grads):
+        if self.one_in:
+            g = grads[0].contiguous()
+            b, _, h, wd = g.shape
+            dx = torch.empty((b, self.cin, h, wd), dtype=torch.float32, device=g.device)
+            with torch.cuda.device(g.device):
+                _lib.check(_lib.load().dv_conv2d_1in_f32(g.data_ptr(), self.wt.data_ptr(), 0, dx.data_ptr(), b, h, wd,
+                                                         self.cin, 3, ACT_NONE, _lib.stream_ptr()), "dv_conv2d_1in_f32")
+            return dx
+        return self.plan(list(grads) if len(grads) > 1 else grads[0])
+
+
+def _split_channels(t: torch.Tensor, sources):
+    """Channel views of ``t`` with the channel counts of ``sources``."""
+    out, c0 = [], 0
+    for s in sources:
+        out.append(t[:, c0:c0 + s.shape[1]])
+        c0 += s.shape[1]
+    return out
+
+
+def _act_grad(g: torch.Tensor, out: torch.Tensor, act: int) -> torch.Tensor:
+    """Gradient before the fused activation, from the activation's saved OUTPUT."""
+    if act == ACT_NONE:
+        return g.contiguous()
+    if act == ACT_RELU:
+        return g * (out > 0)
+    if act == ACT_SIGMOID:
+        return g * out * (1.0 - out)
+    if act == ACT_TANH:
+        return g * (1.0 - out * out)
+    raise _lib.DiffuVolumeError(f"no derivative for activation {act}")
+
+
+class TrainConvPlan:
+    """One nn.Conv2d (3x3 padding 1, or 1x1; stride 1) of the update block for the training route: the forward plan with
+    bias and activation fused, and the packed weights of its input gradient."""
+
+    def __init__(self, conv: torch.nn.Conv2d, act: int):
+        k = conv.kernel_size[0]
+        if conv.kernel_size != (k, k) or k not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or \
+                conv.padding != ((k - 1) // 2,) * 2 or conv.groups != 1:
+            raise _lib.DiffuVolumeError(f"TrainConvPlan: 3x3 (padding 1) or 1x1, stride 1, dilation 1 only, got {conv}")
+        _check(conv.weight, "weight")
+        self.k, self.act, self.cout = k, act, conv.out_channels
+        self.fwd = Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
+        self.bwd = _InputGradPlan([conv.weight])
+
+
+class ConvCatFn(torch.autograd.Function):
+    """act(conv(cat(sources)) + bias) on the HIP kernels, all three gradients on the HIP kernels."""
+
+    @staticmethod
+    def forward(ctx, plan, weight, bias, *sources):
+        for t in sources:
+            _check(t, "source")
+        sources = [t.contiguous() for t in sources]
+        out = plan.fwd(sources if len(sources) > 1 else sources[0])
+        ctx.plan = plan
+        ctx.save_for_backward(out, *sources)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, *sources = ctx.saved_tensors
+        plan = ctx.plan
+        gp = _act_grad(g, out, plan.act)
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            # (DispHead.conv2, 256 -> 1, idles 63 of the tile's 64 rows; measured at batch 4, 80x184: 0.205 ms here against
+            # 0.261 ms on dv_conv2d_wgrad_f32, so it stays on this kernel: a 1 x 2304 reduction is not worth a route)
+            dw = conv2d_cat_weight_grad(sources, gp, plan.k)
+        if ctx.needs_input_grad[2]:
+            db = gp.sum(dim=(0, 2, 3))
+        dsrc = [None] * len(sources)
+        if any(ctx.needs_input_grad[3:]):
+            dx = plan.bwd([gp])
+            dsrc = [v if need else None for v, need in zip(_split_channels(dx, sources), ctx.needs_input_grad[3:])]
+        return (None, dw, db, *dsrc)
+
+
+class Conv1InFn(torch.autograd.Function):
+    """relu(conv(x) + bias) of a single-input-channel k x k convolution (BasicMotionEncoder.convd1, 7x7): forward on
+    ``dv_conv2d_1in_f32`` (the inference kernel), weight gradient on ``dv_conv2d_1in_wgrad_f32`` (fixed summation order:
+    MIOpen's backward-weights of this shape does not return the same bits twice).  The input gradient -- the reference
+    always detaches ``disp`` -- is a 64 -> 1 convolution left to PyTorch."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _check(x, "disp")
+        _check(weight, "weight")
+        x, wt = x.contiguous(), weight.detach().contiguous()
+        b, cin, h, w = x.shape
+        k = int(wt.shape[-1])
+        if cin != 1 or wt.shape[1] != 1 or k != 7:
+            raise _lib.DiffuVolumeError(f"Conv1InFn: one input channel, k = 7, got {tuple(wt.shape)}")
+        out = torch.empty((b, wt.shape[0], h, w), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dv_conv2d_1in_f32(x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
+                                                     out.shape[1], k, ACT_RELU, _lib.stream_ptr()), "dv_conv2d_1in_f32")
+        ctx.save_for_backward(x, weight, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, out = ctx.saved_tensors
+        gp = _act_grad(g, out, ACT_RELU)
+        b, _, h, w = x.shape
+        k = int(weight.shape[-1])
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().dv_conv2d_1in_wgrad_f32(x.data_ptr(), gp.data_ptr(), dw.data_ptr(), b, h, w,
+                                                               weight.shape[0], k, _lib.stream_ptr()), "dv_conv2d_1in_wgrad_f32")
+        if ctx.needs_input_grad[2]:
+            db = gp.sum(dim=(0, 2, 3))
+        if ctx.needs_input_grad[0]:
+            dx = F.conv2d(gp, weight.detach().flip(2, 3).transpose(0, 1), None, padding=k // 2)
+        return dx, dw, db
+
+
+def conv_1in_relu(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """relu(conv(x)) for a single-input-channel layer on the training route."""
+    if route() == "torch":
+        return F.relu(conv(x))
+    return Conv1InFn.apply(x, conv.weight, conv.bias)
+
+
+def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources) -> torch.Tensor:
+    """act(conv(cat(sources))) for the training route of the update block.  ``plan``: a callable that returns the
+    layer's TrainConvPlan; it is only called (and the plan only built) on the HIP route."""
+    sources = list(sources) if isinstance(sources, (list, tuple)) else [sources]
+    if route() == "torch":
+        x = torch.cat(sources, dim=1) if len(sources) > 1 else sources[0]
+        y = F.conv2d(x, conv.weight, conv.bias, padding=(conv.kernel_size[0] - 1) // 2)
+        return {ACT_NONE: lambda t: t, ACT_RELU: F.relu, ACT_SIGMOID: torch.sigmoid, ACT_TANH: torch.tanh}[act](y)
+    p = plan()
+    assert p.act == act
+    return ConvCatFn.apply(p, conv.weight, conv.bias, *sources)
+
+
+def _gates(fn: str, *args) -> None:
+    with torch.cuda.device(args[0].device):
+        _lib.check(getattr(_lib.load(), fn)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                                            _lib.stream_ptr()), fn)
+
+
+class GRUTrainPlan:
+    """A ConvGRU for the training route: the z | r pair launch (sigmoid fused, no ``mul``), the candidate's plan (tanh
+    fused, no blend) and the packed weights of the two input gradients."""
+
+    def __init__(self, gru):
+        for c in (gru.convz, gru.convr, gru.convq):
+            _check(c.weight, "weight")
+        self.hidden = gru.convz.out_channels
+        self.zr = Conv2dPairPlan((gru.convz.weight, gru.convz.bias), (gru.convr.weight, gru.convr.bias), ACT_SIGMOID)
+        self.q = Conv2dPlan(gru.convq.weight, None, dilation=1, act=ACT_TANH, bias=gru.convq.bias)
+        self.zr_bwd = _InputGradPlan([gru.convz.weight, gru.convr.weight])
+        self.q_bwd = _InputGradPlan([gru.convq.weight])
+
+
+class ConvGRUFn(torch.autograd.Function):
+    """One ConvGRU call (update.py:33-40).  Saved for the backward: h, the x sources, z, r, q -- no concatenation, no
+    r*h, no 1-z or z*q.  Inputs: plan, six parameters, h, cz, cr, cq, then the x sources."""
+
+    @staticmethod
+    def forward(ctx, plan, wz, bz, wr, br, wq, bq, h, cz, cr, cq, *xs):
+        for t in (h, cz, cr, cq, *xs):
+            _check(t, "ConvGRU input")
+        h, cz, cr, cq = (t.contiguous() for t in (h, cz, cr, cq))
+        xs = [t.contiguous() for t in xs]
+        z, r = plan.zr([h, *xs], residual=(cz, cr))
+        rh = torch.empty_like(h)
+        _gates("dv_gru_reset_mul_f32", r, h, rh, h.numel())
+        q = plan.q([rh, *xs], residual=cq)
+        out = torch.empty_like(h)
+        _gates("dv_gru_blend_f32", z, q, h, out, h.numel())
+        ctx.plan = plan
+        ctx.save_for_backward(h, z, r, q, *xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        h, z, r, q, *xs = ctx.saved_tensors
+        plan = ctx.plan
+        need = ctx.needs_input_grad
+        g = g.contiguous()
+        n = h.numel()
+        dq, dz, dh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
+        _gates("dv_gru_gates_bwd_blend_f32", g, z, q, h, dq, dz, dh, n)
+        rh = torch.empty_like(h)
+        _gates("dv_gru_reset_mul_f32", r, h, rh, n)                   # (recomputed: the forward's bits)
+        dq_in = plan.q_bwd([dq])                                      # d[rh | x...]
+        dr = torch.empty_like(h)
+        _gates("dv_gru_gates_bwd_reset_f32", dq_in[:, :plan.hidden].contiguous(), r, h, dr, dh, n)
+        dzr_in = plan.zr_bwd([dz, dr])                                # d[h | x...]
+        dh += dzr_in[:, :plan.hidden]
+        hx = [h, *xs]
+        dwz = conv2d_cat_weight_grad(hx, dz, 3) if need[1] else None
+        dwr = conv2d_cat_weight_grad(hx, dr, 3) if need[3] else None
+        dwq = conv2d_cat_weight_grad([rh, *xs], dq, 3) if need[5] else None
+        dbz = dz.sum(dim=(0, 2, 3)) if need[2] else None
+        dbr = dr.sum(dim=(0, 2, 3)) if need[4] else None
+        dbq = dq.sum(dim=(0, 2, 3)) if need[6] else None
+        dxs, c0 = [], plan.hidden
+        for t, nd in zip(xs, need[11:]):
+            c1 = c0 + t.shape[1]
+            dxs.append(dq_in[:, c0:c1] + dzr_in[:, c0:c1] if nd else None)
+            c0 = c1
+        return (None, dwz, dbz, dwr, dbr, dwq, dbq, dh if need[7] else None, dz if need[8] else None,
+                dr if need[9] else None, dq if need[10] else None, *dxs)
+
+
+def conv_gru(plan, gru, h, cz, cr, cq, *xs) -> torch.Tensor:
+    """ConvGRU.forward for the training route (the reference's expression under DV_TRAIN_CONV2D=torch).  ``plan``: a
+    callable that returns the GRUTrainPlan, only called on the HIP route."""
+    if route() == "torch":
+        x = torch.cat(xs, dim=1)
+        hx = torch.cat([h, x], dim=1)
+        z = torch.sigmoid(gru.convz(hx) + cz)
+        r = torch.sigmoid(gru.convr(hx) + cr)
+        q = torch.tanh(gru.convq(torch.cat([r * h, x], dim=1)) + cq)
+        return (1 - z) * h + z * q
+    if len(xs) > 3:                                     # the kernels take four sources: [h | x1 | x2 | x3]
+        xs = (torch.cat(xs[:-2], dim=1),) + tuple(xs[-2:])
+    c = gru.convz, gru.convr, gru.convq
+    return ConvGRUFn.apply(plan(), c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias, h, cz, cr, cq, *xs)

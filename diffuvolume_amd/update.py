@@ -15,6 +15,16 @@ points of the reference's fp16 tensors: convolution operands and outputs, and ev
 epilogues, are rounded to fp16.  Storage stays float32 (fp16-exact values); fp16 input tensors are converted to float32
 on entry.  The motion features' channel 127 carries the float32 ``disp`` unrounded, as the reference's
 ``torch.cat([out, disp])`` promotes to float32 under autocast (update.py:94).  bf16 autocast is refused.
+
+Training (``module.train()`` with gradients enabled): ``BasicMultiUpdateBlock.forward`` takes the differentiable route of
+``train2d`` -- the same forward kernels with ReLU / sigmoid / tanh fused, one ``train2d.ConvGRUFn`` per ConvGRU (gate
+arithmetic and its backward on csrc/conv2d_wgrad_cat.hip's elementwise kernels), weight gradients on
+``dv_conv2d_wgrad_cat_f32`` over the virtual concatenations, input gradients on the forward kernels with flipped weights
+packed once per weight key (the ``plans("train")`` slot).  ``convd1`` (7x7, one input channel) runs through autograd
+there (``train2d.Conv1InFn``) so that it learns although ``disp`` is detached; ``pool2x`` / ``interp`` keep their
+autograd dispatch.  fp32 only:
+fp16 autocast raises.  ``DV_TRAIN_CONV2D=torch`` sends the convolutions and the gate arithmetic to torch expressions.
+Train mode under ``torch.no_grad()`` runs the inference kernels.
 """
 from __future__ import annotations
 
@@ -40,9 +50,12 @@ def autocast_f16() -> bool:
 
 class _Planned(PlanCache, nn.Module):
     """Two plan slots (submodule.PlanCache): the fp32 plans (``plans()``) and the fp16-autocast ones (``plans("f16")``),
-    each built lazily by the module's ``_build`` / ``_build16``."""
+    each built lazily by the module's ``_build`` / ``_build16``, and the training route's (``plans("train")``,
+    ``_build_train``: forward plans plus the packed weights of the input gradients)."""
 
     def _build_plans(self, slot):
+        if slot == "train":
+            return self._build_train()
         return self._build16() if slot == "f16" else self._build()
 
 
@@ -73,7 +86,16 @@ class DispHead(_Planned):
     def _build16(self):
         return _plan16(self.conv1, ACT_RELU), _plan16(self.conv2, ACT_NONE)
 
+    def _build_train(self):
+        from .train2d import TrainConvPlan
+        return TrainConvPlan(self.conv1, ACT_RELU), TrainConvPlan(self.conv2, ACT_NONE)
+
     def forward(self, x):
+        if _training(self):
+            from .train2d import conv_cat
+            _train_entry(self)
+            return conv_cat(lambda: self.plans("train")[1], self.conv2, ACT_NONE,
+                            conv_cat(lambda: self.plans("train")[0], self.conv1, ACT_RELU, x))
         c1, c2 = self.plans("f16") if autocast_f16() else self.plans()
         return c2(c1(_f32(x)))
 
@@ -99,7 +121,15 @@ class ConvGRU(_Planned):
         return (Conv2dF16Plan(self.convz.weight, self.convz.bias, ACT_SIGMOID, pair=(self.convr.weight, self.convr.bias)),
                 _plan16(self.convq, ACT_TANH))
 
+    def _build_train(self):
+        from .train2d import GRUTrainPlan
+        return GRUTrainPlan(self)
+
     def forward(self, h, cz, cr, cq, *x_list):
+        if _training(self):
+            from .train2d import conv_gru
+            _train_entry(self)
+            return conv_gru(lambda: self.plans("train"), self, h, cz, cr, cq, *x_list)
         if autocast_f16():
             # (the fp16 plans round z, r*h and the blend (1-z)*h + z*q at the reference's points; see csrc/conv2d_f16.hip)
             pzr, pq = self.plans("f16")
@@ -153,11 +183,33 @@ class BasicMotionEncoder(_Planned):
                                   torch.cat([b, b.new_zeros(1)]), act=ACT_RELU)
         return p
 
+    def _build_train(self):
+        from .train2d import TrainConvPlan
+        return {n: TrainConvPlan(getattr(self, n), ACT_RELU) for n in ("convc1", "convc2", "convd2", "conv")}
+
     def forward(self, disp, corr):
         return self.features(disp, corr)                # update.py:94 (the reference's return value)
 
+    def _features_train(self, disp, corr):
+        """features() on the differentiable route: the real [127, 128, 3, 3] weight of `conv` (no padded channel, nothing
+        written in place into a saved tensor) and the reference's torch.cat([out, disp]); convd1 through autograd
+        (train2d.Conv1InFn: the inference kernel and a small fixed-order weight-gradient kernel), so that its weight and
+        bias learn although `disp` is detached."""
+        from .geometry_ddim import GeoLookupRequest
+        from .train2d import conv_1in_relu, conv_cat
+        _train_entry(self)
+        p = lambda n: (lambda: self.plans("train")[n])
+        if isinstance(corr, GeoLookupRequest):
+            corr = corr.materialize()              # the fused lookup + 1x1 is inference-only
+        cor = conv_cat(p("convc2"), self.convc2, ACT_RELU, conv_cat(p("convc1"), self.convc1, ACT_RELU, corr))
+        disp_ = conv_cat(p("convd2"), self.convd2, ACT_RELU, conv_1in_relu(self.convd1, disp))
+        out = conv_cat(p("conv"), self.conv, ACT_RELU, [cor, disp_])
+        return torch.cat([out, disp], dim=1)
+
     def features(self, disp, corr):
         """The motion features [B,128,h,w] = [conv output (127) | disp (1)], update.py:88-94."""
+        if _training(self):
+            return self._features_train(disp, corr)
         if autocast_f16():
             return self._features16(_f32(disp), _f32(corr))
         p = self.plans()
@@ -202,6 +254,25 @@ class BasicMotionEncoder(_Planned):
             _lib.check(getattr(_lib.load(), fn)(disp.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
                                                 out.shape[1], int(wt.shape[-1]), ACT_RELU, _lib.stream_ptr()), fn)
         return out
+
+
+def _training(m) -> bool:
+    """The differentiable route: train mode AND gradients enabled (train mode under no_grad runs the inference kernels:
+    the block has no layer that behaves differently in training)."""
+    return m.training and torch.is_grad_enabled()
+
+
+def _train_entry(m):
+    """Every module of the block is a training entry of its own (ConvGRU, DispHead, BasicMotionEncoder called directly):
+    fp32 only, and the packed weights follow the weight key, so an optimizer step since the last call drops them here."""
+    _no_autocast()
+    m.refresh_plans()
+
+
+def _no_autocast():
+    if torch.is_autocast_enabled("cuda"):
+        raise _lib.DiffuVolumeError("the update block trains in float32: fp16 / bf16 autocast is not supported in train "
+                                    "mode (mixed-precision training is not implemented)")
 
 
 def _hip_ok(x, what):
@@ -269,6 +340,39 @@ class BasicMultiUpdateBlock(_Planned):
     def _build16(self):
         return _plan16(self.mask_feat_4[0], ACT_RELU)
 
+    def _build_train(self):
+        from .train2d import TrainConvPlan
+        return TrainConvPlan(self.mask_feat_4[0], ACT_RELU)
+
+    def _forward_train(self, net, inp, corr, disp, iter04, iter08, iter16, update, mask):
+        """The reference's forward (update.py:121-142) on the differentiable route, one stream.  The plans of the whole
+        block follow the weight key: an optimizer step between two calls drops them here."""
+        from .train2d import _check, conv_cat
+        _train_entry(self)
+        for t in (*net, *(t for level in inp for t in level), disp):
+            if isinstance(t, torch.Tensor):
+                _check(t, "update block input")
+        if isinstance(corr, torch.Tensor):
+            _check(corr, "corr")
+        if iter16:
+            net[2] = self.gru16(net[2], *(inp[2]), pool2x(net[1]))
+        if iter08:
+            if self.args.n_gru_layers > 2:
+                net[1] = self.gru08(net[1], *(inp[1]), pool2x(net[0]), interp(net[2], net[1]))
+            else:
+                net[1] = self.gru08(net[1], *(inp[1]), pool2x(net[0]))
+        if iter04:
+            mf = self.encoder(disp, corr)
+            if self.args.n_gru_layers > 1:
+                net[0] = self.gru04(net[0], *(inp[0]), mf, interp(net[1], net[0]))
+            else:
+                net[0] = self.gru04(net[0], *(inp[0]), mf)
+        if not update:
+            return net
+        delta_disp = self.disp_head(net[0])
+        mask_feat_4 = conv_cat(lambda: self.plans("train"), self.mask_feat_4[0], ACT_RELU, net[0]) if mask else None
+        return net, mask_feat_4, delta_disp
+
     import os as _os
     OVERLAP = _os.environ.get("DV_IGEV_OVERLAP", "1") != "0"
     _streams = None
@@ -284,8 +388,8 @@ class BasicMultiUpdateBlock(_Planned):
                 mask=True):
         """The reference's call (update.py:119-142) plus `mask=False` to skip `mask_feat_4`, which the reference computes
         in every iteration and reads only after the last one (igev_stereo_ddim.py:255-259)."""
-        if self.training:
-            raise NotImplementedError("the MI355X update block is inference-only (model.eval())")
+        if _training(self):
+            return self._forward_train(net, inp, corr, disp, iter04, iter08, iter16, update, mask)
         with torch.no_grad():
             mixed = autocast_f16()
             if mixed:             # an autocast caller's fp16 tensors: float32 once, here (the list objects are kept)

@@ -552,6 +552,43 @@ size_t dv_conv2d_wgrad_workspace_floats(int B, int Cin, int H, int W, int Cout, 
 int dv_conv2d_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int H, int W,
                         int Cout, int k, int dilation, dv_stream_t stream);
 
+/* ---- training: weight gradient of the update block's convolutions (csrc/conv2d_wgrad_cat.hip) ----------
+ * The backward of ConvGRU's convz / convr / convq (KITTI15/core/update.py:26-40), of BasicMotionEncoder's convc1 /
+ * convc2 / convd2 / conv (update.py:74-94), of DispHead.conv1 (update.py:15-24) and of mask_feat_4 (update.py:115-117)
+ * with respect to the weights, over the VIRTUAL channel concatenation of dv_conv2d_cat_f32:
+ *   dw[co, ci, ky, kx] = sum_{b, y, x} g[b, co, y, x] * X[b, ci, y + ky - p, x + kx - p],   X = cat(inputs, dim=1)
+ * (k in {1, 3}, p = (k-1)/2, stride 1, dilation 1, X zero outside the image).  `inputs` / `channels` are HOST arrays of
+ * n_inputs (1..4) device pointers [B,channels[i],H,W] and their channel counts (any positive counts); g [B,Cout,H,W];
+ * dw [Cout, sum(channels), k, k]; all fp32 and contiguous.  Implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32),
+ * 64 x 64 block tiles, staging double-buffered through registers; the K dimension (bricks of 2 x 32 output positions of
+ * the whole batch) is split over blocks, every split writes its partial into `workspace`
+ * (dv_conv2d_wgrad_cat_workspace_floats floats = splits * Cout * Cin * k * k, at most 48 MB; 0 = unsupported arguments)
+ * and a second kernel sums the splits in split order -- no atomics, the same bits on every launch of a shape. */
+size_t dv_conv2d_wgrad_cat_workspace_floats(const int* channels, int n_inputs, int B, int H, int W, int Cout, int k);
+int dv_conv2d_wgrad_cat_f32(const float* const* inputs, const int* channels, int n_inputs, const float* g, float* dw,
+                            float* workspace, int B, int H, int W, int Cout, int k, dv_stream_t stream);
+
+/* ConvGRU gate arithmetic of the training route (update.py:36-39), elementwise over n floats (float4 bodies on 16-byte
+ * aligned pointers, scalar otherwise):
+ *   dv_gru_reset_mul_f32        rh = r * h
+ *   dv_gru_blend_f32            out = h + z * (q - h)   -- (1 - z) h + z q in the form, and with the rounding, of
+ *                               dv_conv2d_gated_f32's blend epilogue: the training forward equals the eval forward's bits
+ *   dv_gru_gates_bwd_blend_f32  dq_pre = dh' z (1 - q^2),  dz_pre = dh' (q - h) z (1 - z),  dh = dh' (1 - z)
+ *   dv_gru_gates_bwd_reset_f32  dr_pre = d(rh) h r (1 - r),  dh += d(rh) r
+ * z, r, q are the gates AFTER their non-linearity; *_pre are gradients of the convolutions' outputs. */
+int dv_gru_reset_mul_f32(const float* r, const float* h, float* rh, size_t n, dv_stream_t stream);
+int dv_gru_blend_f32(const float* z, const float* q, const float* h, float* out, size_t n, dv_stream_t stream);
+int dv_gru_gates_bwd_blend_f32(const float* dh_new, const float* z, const float* q, const float* h, float* dq_pre,
+                               float* dz_pre, float* dh, size_t n, dv_stream_t stream);
+int dv_gru_gates_bwd_reset_f32(const float* drh, const float* r, const float* h, float* dr_pre, float* dh, size_t n,
+                               dv_stream_t stream);
+
+/* Weight gradient of the single-input-channel convolution of dv_conv2d_1in_f32 (BasicMotionEncoder.convd1, 7x7,
+ * KITTI15/core/update.py:78, :91): dw[co, 0, ky, kx] = sum_{b,y,x} g[b,co,y,x] * x[b,0,y+ky-p,x+kx-p], k = 7,
+ * p = 3; x [B,1,H,W], g [B,Cout,H,W], dw [Cout,1,k,k].  Fixed summation order, no atomics. */
+int dv_conv2d_1in_wgrad_f32(const float* x, const float* g, float* dw, int B, int H, int W, int Cout, int k,
+                            dv_stream_t stream);
+
 /* ---- metrics (SceneFlow/utils/metrics.py:22-65) -------------------------------
  * Per-image sums over pixels with mask!=0: sums[b] = { n_mask, n_gt_pos, sum|gt-est|,
  * n_D1 (err>3 & err/|gt|>0.05), n_err>1, n_err>2, n_err>3, 0 } as fp64 [B,8].
