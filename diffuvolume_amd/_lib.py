@@ -126,6 +126,13 @@ SIGNATURES = {
     "dv_masked_metrics_f32": (c_int, [P, P, P, P, I, I, P]),
     "dv_conv3d_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I, I]),
     "dv_conv3d_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "dv_deconv3d_k4s2_dgrad_packed_floats": (c_size_t, [I, I]),
+    "dv_deconv3d_k4s2_dgrad_pack_weights_f32": (c_int, [P, P, I, I, P]),
+    "dv_deconv3d_k4s2_dgrad_f32": (c_int, [P, P, P, I, I, I, I, I, I, P]),
+    "dv_deconv3d_k4s2_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I]),
+    "dv_deconv3d_k4s2_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
+    "dv_feature_gate_bwd_workspace_floats": (c_size_t, [I, I, I, I, I]),
+    "dv_feature_gate_bwd_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, P]),
     "dv_conv2d_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I]),
     "dv_conv2d_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "dv_conv2d_wgrad_cat_workspace_floats": (c_size_t, [P, I, I, I, I, I, I]),

@@ -21,11 +21,11 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, train2d, train3d
 from .acv_ddim import cosine_beta_schedule
 from .head import SinusoidalPositionEmbeddings
 from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv2dK4S2Plan, Deconv3dPlan, PlanCache, _dev_f32, build_gwc_volume,
-                        feature_gate, softmax_regress, weight_key)
+                        _gwc_volume_autograd, feature_gate, softmax_regress, weight_key)
 
 
 class DynamicHead180(nn.Module):
@@ -289,6 +289,12 @@ def _wants_autograd(x) -> bool:
     return torch.is_grad_enabled() and x.requires_grad
 
 
+def _train_mode(m: nn.Module) -> bool:
+    """The training route of a volume-side module, decided per module like the update block's (update.py): the module is
+    in train mode and autograd records.  Not ``x.requires_grad``: a frozen backbone still trains the volume weights."""
+    return m.training and torch.is_grad_enabled()
+
+
 def _bn_tuple(bn):
     return None if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
 
@@ -434,6 +440,19 @@ class BasicConv(nn.Module):
             return Deconv3dPlan(self.conv.weight, bn, act=act, eps=self.bn.eps)
         return Conv3dPlan(self.conv.weight, bn, stride=self.conv.stride[0], act=act, eps=self.bn.eps)
 
+    def train_forward(self, x):
+        """The training route: the convolution as an autograd function on the HIP kernels (train3d / train2d), BatchNorm
+        on batch statistics (running buffers updated) and LeakyReLU in PyTorch.  No plan is built or refreshed."""
+        if self.is_3d:
+            x = (train3d.conv_transpose3d_module if self.deconv else train3d.conv3d_module)(self.conv, x)
+        elif self.deconv:
+            raise _lib.DiffuVolumeError("the training route has no 2-D transposed BasicConv")
+        else:
+            x = train2d.conv2d_module(self.conv, x)
+        if self.use_bn:
+            x = self.bn(x)
+        return F.leaky_relu(x, 0.01) if self.relu else x
+
     def forward(self, x):
         if self.is_3d:
             raise _lib.DiffuVolumeError("3-D BasicConv runs through its HIP plan, not nn.Module.forward")
@@ -454,6 +473,9 @@ class FeatureAtt(nn.Module):
                                       nn.Conv2d(feat_chan // 2, cv_chan, 1))
 
     def forward(self, cv, feat, inplace=False):
+        if _train_mode(self):                   # out of place: the gate's backward reads the ungated volume
+            logit = train2d.conv2d_module(self.feat_att[1], self.feat_att[0].train_forward(feat))
+            return train3d.feature_gate_train(cv, logit)
         return feature_gate(cv, hip_sequential(self.feat_att, feat), inplace=inplace)
 
 
@@ -464,6 +486,12 @@ def _seq_plans(seq):
 def _run(plans, x):
     for p in plans:
         x = p(x)
+    return x
+
+
+def _run_train(seq, x):
+    for m in seq:
+        x = m.train_forward(x)
     return x
 
 
@@ -501,7 +529,19 @@ class hourglass(PlanCache, nn.Module):
             p[n] = getattr(self, n).plan()
         return p
 
+    def _train_forward(self, x, features):
+        conv1 = self.feature_att_8(_run_train(self.conv1, x), features[1])
+        conv2 = self.feature_att_16(_run_train(self.conv2, conv1), features[2])
+        conv3 = self.feature_att_32(_run_train(self.conv3, conv2), features[3])
+        conv2 = _run_train(self.agg_0, torch.cat((self.conv3_up.train_forward(conv3), conv2), dim=1))
+        conv2 = self.feature_att_up_16(conv2, features[2])
+        conv1 = _run_train(self.agg_1, torch.cat((self.conv2_up.train_forward(conv2), conv1), dim=1))
+        conv1 = self.feature_att_up_8(conv1, features[1])
+        return self.conv1_up.train_forward(conv1)
+
     def forward(self, x, features):
+        if _train_mode(self):
+            return self._train_forward(x, features)
         p = self.plans()
         conv1 = self.feature_att_8(_run(p["conv1"], x), features[1], inplace=True)
         conv2 = self.feature_att_16(_run(p["conv2"], conv1), features[2], inplace=True)
@@ -520,12 +560,36 @@ def _cost_volume_plans(m):
 def _cost_volume(m, match_left, match_right, features_left, max_disp):
     """IGEVStereo_ddim :378-386 on the modules of ``m`` (an IGEVCostVolume or the IGEVStereo_ddim itself): gwc (8 groups)
     -> corr_stem -> FeatureAtt -> hourglass(8) -> classifier -> softmax + regression."""
+    if _train_mode(m):
+        return _cost_volume_train(m, match_left, match_right, features_left, max_disp)
     m.refresh_plans()
     stem, classifier = m.plans()
     gwc = stem(build_gwc_volume(match_left, match_right, max_disp // 4, 8))
     gwc = m.corr_feature_att(gwc, features_left[0], inplace=True)
     geo = m.cost_agg(gwc, features_left)
     return geo, softmax_regress(classifier(geo)).unsqueeze(1)          # F.softmax + disparity_regression :382-383
+
+
+def _cost_volume_train(m, match_left, match_right, features_left, max_disp):
+    """The same front for training (train mode with autograd recording): every convolution and gate an autograd function
+    on the HIP kernels, BatchNorm / LeakyReLU / softmax / regression PyTorch, the gwc volume its differentiable expression
+    (whether or not the features ask for gradients, so that a frozen backbone gives the same bits)."""
+    for name, t in (("match_left", match_left), ("match_right", match_right),
+                    *((f"features_left[{i}]", f) for i, f in enumerate(features_left))):
+        if not t.is_cuda:
+            raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
+    if match_left.dim() != 4 or match_left.shape != match_right.shape:
+        raise RuntimeError(f"feature shapes differ or are not 4-D: {tuple(match_left.shape)} vs {tuple(match_right.shape)}")
+    d, (h, w) = max_disp // 4, match_left.shape[2:]
+    if d % 8 or h % 8 or w % 8:
+        raise _lib.DiffuVolumeError(f"training the cost-volume front needs d, h, w of the 1/4-resolution volume to be "
+                                    f"multiples of 8 (three stride-2 levels whose skips are concatenated), got {d} x {h} x {w}")
+    gwc = _gwc_volume_autograd(match_left, match_right, d, 8)
+    gwc = m.corr_feature_att(m.corr_stem.train_forward(gwc), features_left[0])
+    geo = m.cost_agg(gwc, features_left)
+    prob = F.softmax(train3d.conv3d_module(m.classifier, geo).squeeze(1), dim=1)            # :382
+    disp_values = torch.arange(0, d, dtype=prob.dtype, device=prob.device).view(1, d, 1, 1)
+    return geo, torch.sum(prob * disp_values, 1, keepdim=True)                               # disparity_regression :383
 
 
 class IGEVCostVolume(PlanCache, nn.Module):

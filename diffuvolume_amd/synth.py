@@ -223,3 +223,46 @@ def update_train_loop(block, x, slow_fast: bool = False):
         disps.append(disp)
         masks.append(mask_feat)
     return loss, disps, masks, net
+
+
+# ---- IGEV's cost-volume front as a training workload (tools/make_golden_igev_volume_train.py, tests,
+# ---- tools/bench_igev_volume_train.py)
+
+IGEV_VOLUME_TRAIN_WEIGHT_SEED = 91
+IGEV_VOLUME_TRAIN_CASES = {"even": dict(seed=41, b=2, h=16, w=32, max_disp=64),
+                           "tall": dict(seed=42, b=2, h=8, w=24, max_disp=192)}
+IGEV_VOLUME_LEAVES = ("match_left", "match_right", "feat0", "feat1", "feat2", "feat3")
+
+
+def igev_volume_train_inputs(seed: int, b: int, h: int, w: int, max_disp: int, dtype=torch.float32, device="cpu",
+                             requires_grad: bool = True, shift: int = 3):
+    """Seeded inputs of one training step of IGEV's cost-volume front at a 1/4 plane of h x w: the 96-channel match
+    features with a correlation ridge (right = left rolled by ``shift`` plus noise), the left feature pyramid (96 / 64 /
+    192 / 160 channels at 1/4 .. 1/32) -- six leaves that require grad unless ``requires_grad=False`` (a frozen
+    backbone) --, a ground truth ``gt`` uniform in [0, D-1] and a standard-normal cotangent ``cot`` of the geometry
+    volume, D = max_disp / 4."""
+    d = max_disp // 4
+
+    def leaf(t):
+        return t.to(device=device, dtype=dtype).requires_grad_(requires_grad)
+    ml = torch.randn(b, 96, h, w, generator=_gen(seed, "ml"))
+    mr = torch.roll(ml, -shift, dims=-1) + 0.1 * torch.randn(b, 96, h, w, generator=_gen(seed, "mr"))
+    feats = [torch.randn(b, c, h // s, w // s, generator=_gen(seed, f"feat{i}"))
+             for i, (c, s) in enumerate(((96, 1), (64, 2), (192, 4), (160, 8)))]
+    gt = torch.rand(b, 1, h, w, generator=_gen(seed, "gt")) * (d - 1)
+    cot = torch.randn(b, 8, d, h, w, generator=_gen(seed, "cot"))
+    return dict(match_left=leaf(ml), match_right=leaf(mr), features=[leaf(f) for f in feats],
+                gt=gt.to(device=device, dtype=dtype), cot=cot.to(device=device, dtype=dtype))
+
+
+def igev_volume_train_leaves(x):
+    """The six leaves of ``igev_volume_train_inputs`` under the names of IGEV_VOLUME_LEAVES."""
+    return dict(zip(IGEV_VOLUME_LEAVES, [x["match_left"], x["match_right"], *x["features"]]))
+
+
+def igev_volume_train_loss(geo: torch.Tensor, init_disp: torch.Tensor, x) -> torch.Tensor:
+    """The `init_disp` term of the reference's sequence_loss (KITTI15/train_stereo.py:33-62) at 1/4 resolution plus a
+    linear functional of the geometry encoding volume, which stands for the GRU terms that reach the weights through the
+    lookup: smooth_l1(init_disp, gt) + mean(geo * cot)."""
+    import torch.nn.functional as F
+    return F.smooth_l1_loss(init_disp, x["gt"]) + (geo * x["cot"]).mean()

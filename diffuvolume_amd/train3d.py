@@ -10,8 +10,12 @@
         1x1x1            conv of g with w^T
     (the kernels pad channel counts internally, so 40 -> 32 layers and the 32 -> 1 head need no padding here);
   * weight gradient: ``dv_conv3d_wgrad_f32`` (csrc/conv3d_wgrad.hip), the transposed form with x and g exchanged.
-BatchNorm and ReLU stay PyTorch.  ``DV_TRAIN_CONV3D=torch`` routes both functions to ``F.conv3d`` /
-``F.conv_transpose3d`` instead (A/B runs, tests).  CPU tensors raise, as everywhere on the hot path."""
+``conv_transpose3d_k4(x, w)`` (k4 s2 p1, bias-free: the IGEV hourglass's conv3_up / conv2_up / conv1_up) has kernels of
+its own for both gradients (csrc/deconv3d_k4_bwd.hip); ``feature_gate_train(cv, logit)`` is FeatureAtt's
+``sigmoid(logit) * cv`` with ``dv_feature_gate_bwd_f32`` as its backward.
+BatchNorm and ReLU stay PyTorch.  ``DV_TRAIN_CONV3D=torch`` routes every function to its torch expression (``F.conv3d``,
+``F.conv_transpose3d``, ``torch.sigmoid(logit).unsqueeze(2) * cv``) instead (A/B runs, tests).  CPU tensors raise, as
+everywhere on the hot path."""
 from __future__ import annotations
 
 import os
@@ -21,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan
+from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan, feature_gate
 
 
 def route() -> str:
@@ -119,6 +123,104 @@ class ConvTranspose3dFn(torch.autograd.Function):
         return dx, dw
 
 
+def deconv3d_k4_input_grad(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """dx [B,Ci,D,H,W] of ConvTranspose3d(k4, s2, p1) with weight ``w`` [Ci,Co,4,4,4] from the output gradient
+    ``g`` [B,Co,2D,2H,2W]."""
+    g, w = g.contiguous(), w.contiguous()
+    b, co, d2, h2, w2 = g.shape
+    ci = w.shape[0]
+    if tuple(w.shape[1:]) != (co, 4, 4, 4) or d2 % 2 or h2 % 2 or w2 % 2:
+        raise _lib.DiffuVolumeError(f"k4 input gradient: weight {tuple(w.shape)} against gradient {tuple(g.shape)}")
+    lib = _lib.load()
+    wp = torch.empty(lib.dv_deconv3d_k4s2_dgrad_packed_floats(ci, co), dtype=torch.float32, device=g.device)
+    dx = torch.empty((b, ci, d2 // 2, h2 // 2, w2 // 2), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        _lib.check(lib.dv_deconv3d_k4s2_dgrad_pack_weights_f32(w.data_ptr(), wp.data_ptr(), ci, co, _lib.stream_ptr()),
+                   "dv_deconv3d_k4s2_dgrad_pack_weights_f32")
+        _lib.check(lib.dv_deconv3d_k4s2_dgrad_f32(g.data_ptr(), wp.data_ptr(), dx.data_ptr(), b, ci, d2 // 2, h2 // 2,
+                                                  w2 // 2, co, _lib.stream_ptr()), "dv_deconv3d_k4s2_dgrad_f32")
+    return dx
+
+
+def deconv3d_k4_weight_grad(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """dW [Ci,Co,4,4,4] of ConvTranspose3d(k4, s2, p1) with input ``x`` [B,Ci,D,H,W] and output gradient ``g``."""
+    x, g = x.contiguous(), g.contiguous()
+    b, ci, d, h, w = x.shape
+    co = g.shape[1]
+    if tuple(g.shape) != (b, co, 2 * d, 2 * h, 2 * w):
+        raise _lib.DiffuVolumeError(f"k4 weight gradient: input {tuple(x.shape)} against gradient {tuple(g.shape)}")
+    lib = _lib.load()
+    n = lib.dv_deconv3d_k4s2_wgrad_workspace_floats(b, ci, d, h, w, co)
+    if n == 0:
+        raise _lib.DiffuVolumeError(f"dv_deconv3d_k4s2_wgrad_f32 does not take the shape {tuple(x.shape)}")
+    dw = torch.empty((ci, co, 4, 4, 4), dtype=torch.float32, device=x.device)
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dv_deconv3d_k4s2_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, ci, d, h,
+                                                  w, co, _lib.stream_ptr()), "dv_deconv3d_k4s2_wgrad_f32")
+    return dw
+
+
+class ConvTranspose3dK4Fn(torch.autograd.Function):
+    """nn.ConvTranspose3d(k=4, stride=2, padding=1, bias=False); weight [Cin,Cout,4,4,4]."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        _check(x, "x")
+        _check(weight, "weight")
+        if weight.dim() != 5 or tuple(weight.shape[2:]) != (4, 4, 4):
+            raise _lib.DiffuVolumeError(f"unsupported ConvTranspose3d kernel {tuple(weight.shape[2:])}")
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        return Deconv3dPlan(weight.detach().contiguous(), None, act=ACT_NONE)(x.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = deconv3d_k4_input_grad(g, w.detach())
+        if ctx.needs_input_grad[1]:
+            dw = deconv3d_k4_weight_grad(x, g)
+        return dx, dw
+
+
+def feature_gate_grads(cv: torch.Tensor, logit: torch.Tensor, g: torch.Tensor):
+    """(dcv, dlogit) of ``sigmoid(logit).unsqueeze(2) * cv`` from the output gradient ``g``."""
+    cv, logit, g = cv.contiguous(), logit.contiguous(), g.contiguous()
+    b, c, d, h, w = cv.shape
+    lib = _lib.load()
+    dcv, dlogit = torch.empty_like(cv), torch.empty_like(logit)
+    n = lib.dv_feature_gate_bwd_workspace_floats(b, c, d, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=cv.device) if n else None
+    with torch.cuda.device(cv.device):
+        _lib.check(lib.dv_feature_gate_bwd_f32(cv.data_ptr(), logit.data_ptr(), g.data_ptr(), dcv.data_ptr(),
+                                               dlogit.data_ptr(), _lib.ptr(ws), b, c, d, h, w, _lib.stream_ptr()),
+                   "dv_feature_gate_bwd_f32")
+    return dcv, dlogit
+
+
+class FeatureGateFn(torch.autograd.Function):
+    """FeatureAtt's gate ``sigmoid(logit)[:, :, None] * cv`` (out of place); the backward recomputes the sigmoid."""
+
+    @staticmethod
+    def forward(ctx, cv, logit):
+        _check(cv, "cv")
+        _check(logit, "logit")
+        if cv.dim() != 5 or tuple(logit.shape) != (cv.shape[0], cv.shape[1], cv.shape[3], cv.shape[4]):
+            raise _lib.DiffuVolumeError(f"gate logits {tuple(logit.shape)} do not match volume {tuple(cv.shape)}")
+        cv, logit = cv.contiguous(), logit.contiguous()
+        ctx.save_for_backward(cv, logit)
+        return feature_gate(cv.detach(), logit.detach(), inplace=False)
+
+    @staticmethod
+    def backward(ctx, g):
+        cv, logit = ctx.saved_tensors
+        dcv, dlogit = feature_gate_grads(cv, logit, g)
+        return (dcv if ctx.needs_input_grad[0] else None), (dlogit if ctx.needs_input_grad[1] else None)
+
+
 def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1) -> torch.Tensor:
     k = weight.shape[2]
     if route() == "torch":
@@ -132,10 +234,28 @@ def conv_transpose3d(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return ConvTranspose3dFn.apply(x, weight)
 
 
+def conv_transpose3d_k4(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    if route() == "torch":
+        return F.conv_transpose3d(x, weight, None, stride=2, padding=1)
+    return ConvTranspose3dK4Fn.apply(x, weight)
+
+
+def feature_gate_train(cv: torch.Tensor, logit: torch.Tensor) -> torch.Tensor:
+    if route() == "torch":
+        return torch.sigmoid(logit).unsqueeze(2) * cv
+    return FeatureGateFn.apply(cv, logit)
+
+
 def conv3d_module(m: torch.nn.Conv3d, x: torch.Tensor) -> torch.Tensor:
     """An nn.Conv3d of the aggregation stack (cubic kernel, padding (k-1)/2) on the differentiable HIP route."""
     return conv3d(x, m.weight, m.bias, stride=m.stride[0])
 
 
 def conv_transpose3d_module(m: torch.nn.ConvTranspose3d, x: torch.Tensor) -> torch.Tensor:
+    """An nn.ConvTranspose3d (stride 2, padding 1, bias-free): kernel 3 with output_padding 1, or kernel 4."""
+    if tuple(m.kernel_size) == (4, 4, 4):
+        if tuple(m.stride) != (2, 2, 2) or tuple(m.padding) != (1, 1, 1) or tuple(m.output_padding) != (0, 0, 0) \
+                or m.bias is not None:
+            raise _lib.DiffuVolumeError(f"ConvTranspose3d kernel 4 on the training route: stride 2, padding 1, no bias; got {m}")
+        return conv_transpose3d_k4(x, m.weight)
     return conv_transpose3d(x, m.weight)

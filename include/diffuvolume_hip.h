@@ -329,6 +329,17 @@ int dv_batch_to_space_f32(const float* in, float* out, int B, int C, int H, int 
 int dv_feature_gate_f32(const float* cv /*[B,C,D,H,W]*/, const float* logit /*[B,C,H,W]*/, float* out,
                         int B, int C, int D, int H, int W, dv_stream_t stream);
 
+/* Backward of dv_feature_gate_f32 (training of FeatureAtt, KITTI15/core/submodule.py:234-239; six gates per forward,
+ * igev_stereo_ddim.py:62-88, :380): with s = sigmoid(logit) recomputed and g = d loss / d out [B,C,D,H,W]
+ *   dcv[b,c,d,y,x] = g * s[b,c,y,x]        dlogit[b,c,y,x] = s (1 - s) * sum_d g[b,c,d,y,x] * cv[b,c,d,y,x]
+ * g and cv are read once each; the d sum runs in ascending order inside one thread.  A plane too small to fill the chip
+ * splits D into contiguous ranges over blocks: partials go to `workspace` (dv_feature_gate_bwd_workspace_floats
+ * floats; 0 = no split, workspace may be NULL) and are added in split order.  No atomics: the same bits on every launch. */
+size_t dv_feature_gate_bwd_workspace_floats(int B, int C, int D, int H, int W);
+int dv_feature_gate_bwd_f32(const float* cv /*[B,C,D,H,W]*/, const float* logit /*[B,C,H,W]*/, const float* g,
+                            float* dcv, float* dlogit, float* workspace, int B, int C, int D, int H, int W,
+                            dv_stream_t stream);
+
 /* The hourglass tail `F.relu(conv6(x) + redir1(skip))` (SceneFlow/models/acv_ddim.py:81-86, :91-92; KITTI12
  * pwcnet_ddim.py:236-248 with Mish) in ONE launch: the 1x1x1 `redir` convolution of the skip tensor is folded into
  * the transposed convolution as extra K-steps.
@@ -538,6 +549,29 @@ int dv_geo_filter_lookup_conv1x1_f32(const float* geo, const float* corr0, const
 size_t dv_conv3d_wgrad_workspace_floats(int B, int Cin, int D, int H, int W, int Cout, int k, int stride);
 int dv_conv3d_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int D, int H,
                         int W, int Cout, int k, int stride, dv_stream_t stream);
+
+/* ---- training: backward of ConvTranspose3d(k4, s2, p1) (csrc/deconv3d_k4_bwd.hip) ---------------------
+ * The hourglass's conv3_up / conv2_up / conv1_up (KITTI15/core/igev_stereo_ddim.py:44-51, BasicConv deconv
+ * core/submodule.py:9-35; 48 -> 32, 32 -> 16, 16 -> 8).  w [Ci,Co,4,4,4], x [B,Ci,D,H,W], g = the output gradient
+ * [B,Co,2D,2H,2W] (zero outside the volume), t in [0,4)^3, all fp32 and contiguous; any D, H, W >= 1 and any channel
+ * counts (tiles are padded inside the kernels).  Exact fp32 on v_mfma_f32_16x16x4_f32, no atomics: the same bits on
+ * every launch.
+ *   input gradient   dx[b,ci,i]  = sum_{co,t} g[b,co,2i-1+t] * w[ci,co,t]   one fma chain of Co*64 products per element;
+ *                    weights packed once per step by dv_deconv3d_k4s2_dgrad_pack_weights_f32
+ *                    (dv_deconv3d_k4s2_dgrad_packed_floats floats).  W % 4 != 0 or pointers off 16 bytes: scalar path.
+ *   weight gradient  dw[ci,co,t] = sum_{b,i} x[b,ci,i] * g[b,co,2i-1+t]     over bricks of 2 x 4 x 8 x positions, the
+ *                    brick range split over blocks: every split writes its partial into `workspace`
+ *                    (dv_deconv3d_k4s2_wgrad_workspace_floats floats = splits * Ci * Co * 64, at most 48 MB; 0 = invalid
+ *                    shape) and a second kernel adds the splits in split order.  Inside a split, blocks of narrow
+ *                    channel tiles deal the brick's rows to 2 or 4 waves whose chains are added in wave order. */
+size_t dv_deconv3d_k4s2_dgrad_packed_floats(int Ci, int Co);
+int dv_deconv3d_k4s2_dgrad_pack_weights_f32(const float* w /*[Ci,Co,4,4,4]*/, float* wpacked, int Ci, int Co,
+                                            dv_stream_t stream);
+int dv_deconv3d_k4s2_dgrad_f32(const float* g, const float* wpacked, float* dx, int B, int Ci, int D, int H, int W,
+                               int Co, dv_stream_t stream);
+size_t dv_deconv3d_k4s2_wgrad_workspace_floats(int B, int Ci, int D, int H, int W, int Co);
+int dv_deconv3d_k4s2_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Ci, int D, int H,
+                               int W, int Co, dv_stream_t stream);
 
 /* ---- training: 2-D convolution weight gradient (csrc/conv2d_wgrad.hip) -------------------------------
  * The backward of the dilated `convbn` / BasicBlock / conv8 layers of refinenet_version3 (KITTI12/models/
