@@ -546,6 +546,10 @@ class PlanCache:
             slots[slot] = p
         return p
 
+    def drop_slot(self, slot):
+        """Drop one slot's plans (a slot that keeps a narrower weight key of its own and found it stale)."""
+        self.__dict__.get("_plan_slots", {}).pop(slot, None)
+
     def refresh_plans(self):
         """Drop every plan in this module's subtree if a weight was written in place or swapped since they were built."""
         key = self._weight_key()
@@ -694,11 +698,19 @@ class Deconv2dK4S2Plan:
 
     def __init__(self, weight: torch.Tensor, bn=None, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
                  eps: float = 1e-5):
+        wc = self.parity_weights(weight)
+        self.cout = wc.shape[0] // 4
+        rep = lambda t: None if t is None else t.detach().repeat_interleave(4)
+        self.conv = Conv2dPlan(wc, None if bn is None else tuple(rep(t) for t in bn), act=act, eps=eps, bias=rep(bias))
+
+    @staticmethod
+    def parity_weights(weight: torch.Tensor) -> torch.Tensor:
+        """[Cin, Cout, 4, 4] -> the [4*Cout, Cin, 3, 3] weights of the four parity convolutions (channel 4 co + 2 a + b
+        is output parity (a, b) of channel co: F.pixel_shuffle's order)."""
         w = _dev_f32(weight.detach(), "weight")                  # [Cin, Cout, 4, 4]
-        if tuple(w.shape[2:]) != (4, 4):
+        if w.dim() != 4 or tuple(w.shape[2:]) != (4, 4):
             raise _lib.DiffuVolumeError("Deconv2dK4S2Plan: kernel 4, stride 2, padding 1")
         cin, cout = w.shape[0], w.shape[1]
-        self.cout = cout
         wc = torch.zeros((cout, 2, 2, cin, 3, 3), dtype=torch.float32, device=w.device)
         tap = {0: {0: 1, -1: 3}, 1: {1: 0, 0: 2}}              # parity -> {input offset: kernel index}
         for a in (0, 1):
@@ -706,9 +718,7 @@ class Deconv2dK4S2Plan:
                 for b in (0, 1):
                     for dx, kx in tap[b].items():
                         wc[:, a, b, :, dy + 1, dx + 1] = w[:, :, ky, kx].t()
-        rep = lambda t: None if t is None else t.detach().repeat_interleave(4)
-        self.conv = Conv2dPlan(wc.reshape(cout * 4, cin, 3, 3), None if bn is None else tuple(rep(t) for t in bn), act=act,
-                               eps=eps, bias=rep(bias))
+        return wc.reshape(cout * 4, cin, 3, 3)
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return torch.nn.functional.pixel_shuffle(self.conv(x), 2)

@@ -266,3 +266,58 @@ def igev_volume_train_loss(geo: torch.Tensor, init_disp: torch.Tensor, x) -> tor
     lookup: smooth_l1(init_disp, gt) + mean(geo * cot)."""
     import torch.nn.functional as F
     return F.smooth_l1_loss(init_disp, x["gt"]) + (geo * x["cot"]).mean()
+
+
+# ---- IGEV's convex-upsampling head as a training workload (tools/make_golden_igev_upsample_train.py, tests,
+# ---- tools/bench_upsample_train.py)
+
+IGEV_UPSAMPLE_TRAIN_WEIGHT_SEED = 93
+IGEV_UPSAMPLE_TRAIN_CASES = {"even": dict(seed=51, b=2, h=8, w=16, iters=3),
+                             "odd": dict(seed=52, b=1, h=5, w=7, iters=2)}
+IGEV_UPSAMPLE_LOGIT_HEADS = ("spx_gru.0.weight", "spx.0.weight")       # what ``logit_gain`` of the fixture scales
+
+
+def igev_upsample_state_dict(template: Mapping[str, torch.Tensor], seed: int, logit_gain: float = 1.0):
+    """``synth_state_dict`` for an IGEVUpsampler, the two 9-logit heads scaled by ``logit_gain``."""
+    return synth_state_dict(template, seed=seed, scale={k: logit_gain for k in IGEV_UPSAMPLE_LOGIT_HEADS})
+
+
+def igev_upsample_train_inputs(seed: int, b: int, h: int, w: int, iters: int, dtype=torch.float32, device="cpu",
+                               requires_grad: bool = True):
+    """Seeded inputs of one training step of IGEV's upsampling head at a 1/4 plane of h x w over ``iters`` GRU
+    iterations: per iteration the update block's mask feature (relu of noise, 32 channels) and disparity, once per step
+    the 1/2-resolution stem (32 channels), the 1/4-resolution left features (96 channels) and the initial disparity --
+    leaves that require grad unless ``requires_grad=False`` -- and a full-resolution ground truth."""
+    def rnd(key, *shape):
+        return torch.randn(*shape, generator=_gen(seed, key))
+
+    def leaf(t):
+        return t.to(device=device, dtype=dtype).requires_grad_(requires_grad)
+    return dict(mask_feat_4=[leaf(torch.relu(rnd(f"mask{i}", b, 32, h, w))) for i in range(iters)],
+                disp=[leaf(rnd(f"disp{i}", b, 1, h, w).abs() * 4) for i in range(iters)],
+                stem_2x=leaf(rnd("stem_2x", b, 32, 2 * h, 2 * w)), feat0=leaf(rnd("feat0", b, 96, h, w)),
+                init_disp=leaf(rnd("init_disp", b, 1, h, w).abs() * 4),
+                gt=(rnd("gt", b, 1, 4 * h, 4 * w).abs() * 16 + 1).to(device=device, dtype=dtype))
+
+
+def igev_upsample_train_leaves(x):
+    """The leaves of ``igev_upsample_train_inputs`` by name: mask_feat_4_<i>, disp_<i>, stem_2x, feat0, init_disp."""
+    out = {}
+    for i, (m, d) in enumerate(zip(x["mask_feat_4"], x["disp"])):
+        out[f"mask_feat_4_{i}"], out[f"disp_{i}"] = m, d
+    out.update(stem_2x=x["stem_2x"], feat0=x["feat0"], init_disp=x["init_disp"])
+    return out
+
+
+def igev_upsample_train_step(model, x):
+    """The upsampling side of the reference's training forward (KITTI15/core/igev_stereo_ddim.py:390-393, :456-457, :462)
+    on ``model`` -- ``model(disp, mask_feat_4, stem_2x)`` is `upsample_disp`, ``model.init_forward(feat0, stem_2x,
+    init_disp)`` the upsampled initial disparity -- with a loss shaped like sequence_loss (KITTI15/train_stereo.py:33-62)
+    at full resolution: mean|init_up - gt| + sum_i 0.9^(T-1-i) mean|disp_up_i - gt|.  Returns (loss, init_up, [disp_up_i])."""
+    iters = len(x["disp"])
+    ups = [model(x["disp"][i], x["mask_feat_4"][i], x["stem_2x"]) for i in range(iters)]
+    init_up = model.init_forward(x["feat0"], x["stem_2x"], x["init_disp"])
+    loss = (init_up - x["gt"]).abs().mean()
+    for i, up in enumerate(ups):
+        loss = loss + 0.9 ** (iters - 1 - i) * (up - x["gt"]).abs().mean()
+    return loss, init_up, ups

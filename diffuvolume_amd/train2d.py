@@ -20,7 +20,14 @@ single-input-channel ``convd1``).  Their weight gradients run
 on ``dv_conv2d_wgrad_cat_f32`` (csrc/conv2d_wgrad_cat.hip) over the un-materialised concatenation; their input gradients
 are ONE forward launch on the output gradient with the flipped / transposed weights, cut into channel views per
 source; the flipped weights are packed once per plan (the module's ``plans("train")`` slot, dropped with the weight
-key), not per call.  Every other 2-D convolution of the training graphs keeps PyTorch autograd."""
+key), not per call.
+
+IGEV's convex-upsampling head (``igev_stereo_ddim.IGEVUpsampler`` in train mode) uses the third part:
+``conv_transpose2d_k4`` / ``conv_transpose2d_module``, a ConvTranspose2d(kernel 4, stride 2, padding 1) whose forward is
+``Deconv2dK4S2Plan``'s (four parity 3x3 convolutions + pixel shuffle), whose input gradient is ONE 3x3 forward launch on
+the pixel-unshuffled output gradient with the flipped parity weights (``TrainDeconvPlan``, packed once per plan) and
+whose weight gradient is ``dv_deconv2d_k4s2_wgrad_f32`` (csrc/deconv2d_k4_bwd.hip).  Every other 2-D convolution of the
+training graphs keeps PyTorch autograd."""
 from __future__ import annotations
 
 import os
@@ -30,7 +37,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan
+from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan, Deconv2dK4S2Plan
 from .train3d import _check
 
 
@@ -388,3 +395,88 @@ def conv_gru(plan, gru, h, cz, cr, cq, *xs) -> torch.Tensor:
         xs = (torch.cat(xs[:-2], dim=1),) + tuple(xs[-2:])
     c = gru.convz, gru.convr, gru.convq
     return ConvGRUFn.apply(plan(), c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias, h, cz, cr, cq, *xs)
+
+
+# ---- IGEV's convex-upsampling head: ConvTranspose2d(kernel 4, stride 2, padding 1) -----------------------------------
+
+def deconv2d_k4_weight_grad(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """dW [Cin, Cout, 4, 4] of a ConvTranspose2d(4, stride 2, padding 1) with input ``x`` [B,Cin,H,W] and output gradient
+    ``g`` [B,Cout,2H,2W]."""
+    _check(x, "x")
+    _check(g, "output gradient")
+    x, g = x.contiguous(), g.contiguous()
+    b, cin, h, w = x.shape
+    cout = g.shape[1]
+    if g.shape[0] != b or tuple(g.shape[2:]) != (2 * h, 2 * w):
+        raise _lib.DiffuVolumeError(f"deconv2d_k4_weight_grad: x {tuple(x.shape)} against g {tuple(g.shape)}")
+    lib = _lib.load()
+    n = lib.dv_deconv2d_k4s2_wgrad_workspace_floats(b, cin, h, w, cout)
+    if n == 0:
+        raise _lib.DiffuVolumeError(f"dv_deconv2d_k4s2_wgrad_f32 does not take x {tuple(x.shape)}, Cout {cout}")
+    dw = torch.empty((cin, cout, 4, 4), dtype=torch.float32, device=x.device)
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dv_deconv2d_k4s2_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
+                                                  cout, _lib.stream_ptr()), "dv_deconv2d_k4s2_wgrad_f32")
+    return dw
+
+
+class TrainDeconvPlan:
+    """A ConvTranspose2d(4, stride 2, padding 1) [+ bias] for the training route: the forward plan (no BatchNorm, no
+    activation) and the packed weights of its input gradient -- the 3x3 convolution of the pixel-unshuffled output gradient
+    with the flipped, transposed parity weights."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        _check(weight, "weight")
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4):
+            raise _lib.DiffuVolumeError(f"TrainDeconvPlan: a [Cin, Cout, 4, 4] weight, got {tuple(weight.shape)}")
+        self.cin, self.cout = int(weight.shape[0]), int(weight.shape[1])
+        self.fwd = Deconv2dK4S2Plan(weight, None, bias=bias)
+        self.bwd = _InputGradPlan([Deconv2dK4S2Plan.parity_weights(weight)])
+
+
+class ConvTranspose2dK4Fn(torch.autograd.Function):
+    """conv_transpose2d(x, weight, bias, stride 2, padding 1) on the HIP kernels, all three gradients too."""
+
+    @staticmethod
+    def forward(ctx, plan, x, weight, bias):
+        _check(x, "x")
+        x = x.contiguous()
+        if x.dim() != 4 or x.shape[1] != plan.cin or tuple(weight.shape) != (plan.cin, plan.cout, 4, 4):
+            raise _lib.DiffuVolumeError(f"conv_transpose2d_k4: x {tuple(x.shape)} against weight {tuple(weight.shape)}")
+        ctx.plan, ctx.has_bias = plan, bias is not None
+        ctx.save_for_backward(x)
+        return plan.fwd(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = g.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dx = ctx.plan.bwd([F.pixel_unshuffle(g, 2)])
+        if ctx.needs_input_grad[2]:
+            dw = deconv2d_k4_weight_grad(x, g)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = g.sum(dim=(0, 2, 3))
+        return None, dx, dw, db
+
+
+def conv_transpose2d_k4(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, plan=None) -> torch.Tensor:
+    """F.conv_transpose2d(x, weight, bias, stride=2, padding=1) for a [Cin, Cout, 4, 4] weight on the training route.
+    ``plan``: a callable that returns the layer's TrainDeconvPlan (a module's ``plans("train")`` slot), only called on the
+    HIP route; without one the plan is built for this call."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4):
+        raise _lib.DiffuVolumeError(f"conv_transpose2d_k4: kernel 4 x 4 only, got a weight of {tuple(weight.shape)}")
+    if route() == "torch":
+        return F.conv_transpose2d(x, weight, bias, stride=2, padding=1)
+    return ConvTranspose2dK4Fn.apply(plan() if plan is not None else TrainDeconvPlan(weight, bias), x, weight, bias)
+
+
+def conv_transpose2d_module(m: torch.nn.ConvTranspose2d, x: torch.Tensor, plan=None) -> torch.Tensor:
+    """An nn.ConvTranspose2d (kernel 4, stride 2, padding 1: IGEV's spx heads) on the differentiable HIP route."""
+    if not isinstance(m, torch.nn.ConvTranspose2d) or m.kernel_size != (4, 4) or m.stride != (2, 2) or \
+            m.padding != (1, 1) or m.output_padding != (0, 0) or m.dilation != (1, 1) or m.groups != 1:
+        raise _lib.DiffuVolumeError(f"conv_transpose2d_module: kernel 4, stride 2, padding 1, no output padding, "
+                                    f"groups 1 only, got {m}")
+    return conv_transpose2d_k4(x, m.weight, m.bias, plan)

@@ -443,6 +443,19 @@ int dv_ddim_step(const float* disp, const float* unc, const float* used, const f
 int dv_context_upsample_f32(const float* disp_low, const float* weights, float* out, int B, int h, int w,
                             float scale, int apply_softmax, dv_stream_t stream);
 
+/* Backward of the above for training (the reference differentiates `upsample_disp` at every GRU iteration:
+ * igev_stereo_ddim.py:203-211 called from the train loop :441-457, and context_upsample core/submodule.py:241-253 on
+ * `init_disp` :462).  grad_out [B,4h,4w]; with nb_k = scale * disp_low[(Y>>2)+ky-1, (X>>2)+kx-1] and p the softmax
+ * recomputed from the logits with the forward's expression (probabilities are never saved):
+ *   d_weights[b,k,Y,X] = p_k (g nb_k - sum_j p_j g nb_j)      (apply_softmax == 0: g nb_k)
+ *   d_disp[b,y,x]      = scale * sum_k s_k[b, y-ky+1, x-kx+1],  s_k[cell] = sum over the cell's 16 pixels of g p_k
+ * d_weights [B,9,4h,4w] or d_disp [B,h,w] may be NULL (not both): that gradient is not computed.  cell_sums: scratch of
+ * B*9*h*w floats (the s_k), required when d_disp is given.  A gather in both passes -- no scatter, no atomics, fixed
+ * summation order: the same bits on every launch.  weights / grad_out / d_weights must be 16-byte aligned. */
+int dv_context_upsample_bwd_f32(const float* disp_low, const float* weights, const float* grad_out, float* d_weights,
+                                float* d_disp, float* cell_sums, int B, int h, int w, float scale, int apply_softmax,
+                                dv_stream_t stream);
+
 /* ---- IGEV: the small per-iteration operators around the ConvGRUs (KITTI15/core/update.py) ----
  * dv_conv2d_1in_f32: nn.Conv2d(1, Cout, k, padding=k/2) + bias + activation on a single-channel image (the motion
  *   encoder's 7x7 `convd1` on the disparity, update.py:86,:92).  in [B,1,H,W]; w [Cout,1,k,k] (k = 3, 5, 7); out [B,Cout,H,W].
@@ -572,6 +585,21 @@ int dv_deconv3d_k4s2_dgrad_f32(const float* g, const float* wpacked, float* dx, 
 size_t dv_deconv3d_k4s2_wgrad_workspace_floats(int B, int Ci, int D, int H, int W, int Co);
 int dv_deconv3d_k4s2_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Ci, int D, int H,
                                int W, int Co, dv_stream_t stream);
+
+/* ---- training: weight gradient of ConvTranspose2d(k4, s2, p1) (csrc/deconv2d_k4_bwd.hip) ---------------
+ * IGEV's `spx_2_gru.conv1` (32 -> 32, BasicConv deconv core/submodule.py:9-35 inside Conv2x :36-76) and `spx_gru`
+ * (64 -> 9 with bias, KITTI15/core/igev_stereo_ddim.py:110-112), differentiated by the reference at every GRU iteration
+ * (`upsample_disp` :203-211 in the train loop :441-457).  w [Ci,Co,4,4], x [B,Ci,H,W], g = the output gradient
+ * [B,Co,2H,2W] (zero outside the image), all fp32 and contiguous; any H, W >= 1 and any channel counts:
+ *   dw[ci,co,ky,kx] = sum_{b,i,j} x[b,ci,i,j] * g[b,co,2i-1+ky,2j-1+kx]
+ * Implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32), M = the 16 taps of one output channel, N = Ci, K = B*H*W, the
+ * stride-2 taps of g gathered from an LDS halo; K (bricks of 4 x 16 input pixels of the whole batch) is split over
+ * blocks, every split writes its partial into `workspace` (dv_deconv2d_k4s2_wgrad_workspace_floats floats =
+ * splits * Ci * Co * 16, at most 48 MB, 16-byte aligned; 0 = invalid shape) and a second kernel adds the splits in split
+ * order -- no atomics, the same bits on every launch of a shape.  (The input gradient runs on the forward kernels.) */
+size_t dv_deconv2d_k4s2_wgrad_workspace_floats(int B, int Ci, int H, int W, int Co);
+int dv_deconv2d_k4s2_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Ci, int H, int W,
+                               int Co, dv_stream_t stream);
 
 /* ---- training: 2-D convolution weight gradient (csrc/conv2d_wgrad.hip) -------------------------------
  * The backward of the dilated `convbn` / BasicBlock / conv8 layers of refinenet_version3 (KITTI12/models/
