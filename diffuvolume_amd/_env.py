@@ -25,6 +25,9 @@ KNOBS = {
                         "torch = the 2-D convolutions of PWCNet_ddim's refinement network and the convolutions and ConvGRU gate "
                         "arithmetic of IGEV's update block in training on F.conv2d / torch expressions instead of "
                         "the HIP forward, input-gradient and weight-gradient kernels (A/B runs, tests)"),
+    "DV_TRAIN_LOOKUP": ("hip", "geometry_ddim.route() when a training-route volume is built and on each of its lookups",
+                        "torch = IGEV's geometry lookup and all-pairs correlation in training as torch expressions (einsum, "
+                        "gather) instead of the HIP forward kernels and their HIP backward kernels (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_stereo_ddim.IGEVDiffusionLoop.use_graph at import",

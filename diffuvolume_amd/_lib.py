@@ -106,6 +106,7 @@ SIGNATURES = {
     "dv_ddim_step": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, POINTER(DvDdimCoef), P]),
     "dv_context_upsample_f32": (c_int, [P, P, P, I, I, I, c_float, I, P]),
     "dv_allpairs_corr_f32": (c_int, [P, P, P, P, I, I, I, I, I, P]),
+    "dv_allpairs_corr_bwd_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, P]),
     "dv_conv2d_1in_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
     "dv_conv2d_1in_f16": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
     "dv_conv2d_f16_packed_bytes": (c_size_t, [I, I, I]),
@@ -120,6 +121,7 @@ SIGNATURES = {
     "dv_conv2d_fewin_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dv_instance_norm_act_f32": (c_int, [P, P, I, I, ctypes.c_float, I, P]),
     "dv_geo_filter_lookup_f32": (c_int, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "dv_geo_filter_lookup_bwd_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "dv_geo_lookup_conv1x1_packed_floats": (c_size_t, [I]),
     "dv_geo_lookup_conv1x1_pack_weights_f32": (c_int, [P, P, I, P]),
     "dv_geo_filter_lookup_conv1x1_f32": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),

@@ -12,20 +12,9 @@
 // with bilinear, zero padding, align_corners=True in pixel units (utils.py:59-77).
 // Quirk kept: the noise row of pixel n is the n-th run of D floats of the flat
 // [B,D,h,w] tensor (raw reshape, geometry_ddim.py:37), not the pixel's own channel column.
-#include "dv_common.h"
+#include "geo_sample.h"
 
 namespace {
-
-// bilinear_sampler + grid_sample(align_corners=True, zeros) along one axis of length n, in the
-// reference's float order: xg = 2x/(n-1) - 1 ; ix = ((xg+1)/2)*(n-1)
-__device__ __forceinline__ void sample_pos(float x, int n, int& i0, float& w0, float& w1) {
-  const float xg = 2.0f * x / (float)(n - 1) - 1.0f;
-  const float ix = ((xg + 1.0f) / 2.0f) * (float)(n - 1);
-  const float fl = floorf(ix);
-  i0 = (int)fl;
-  w0 = (fl + 1.0f) - ix;   // weight of i0   (ix_ne - ix)
-  w1 = ix - fl;            // weight of i0+1
-}
 
 // Round 3: the taps of a pixel overlap -- level 0 touches disparities floor(d) - 5 .. floor(d) + 6 and level 1 (pairs of
 // them) 2 floor(d/2) - 10 .. 2 floor(d/2) + 13 -- so a thread first copies the 24 entries dlo .. dlo + 23, dlo =
@@ -40,7 +29,6 @@ __device__ __forceinline__ void sample_pos(float x, int n, int& i0, float& w0, f
 // wave walks the planes k = min(dlo) .. max(dlo) + 23 of its 64 pixels TOGETHER: every lane loads plane k at its own pixel
 // (one 256-byte segment per instruction, whatever the disparities are) and keeps the value if k lies in its window.  Smooth
 // disparity: 24-26 coalesced loads per channel; the worst case is the D planes of the channel once.
-constexpr int GEO_WIN = 24;
 constexpr int GEO_BATCH = 8;        // planes requested per round trip
 
 // FUSED: the lookup together with the 1x1 convolution that is its only consumer in IGEV's update block

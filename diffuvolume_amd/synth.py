@@ -321,3 +321,51 @@ def igev_upsample_train_step(model, x):
     for i, up in enumerate(ups):
         loss = loss + 0.9 ** (iters - 1 - i) * (up - x["gt"]).abs().mean()
     return loss, init_up, ups
+
+
+# ---- IGEV's geometry lookup as a training workload (tools/make_golden_igev_lookup_train.py, tests,
+# ---- tools/bench_lookup_train.py)
+
+IGEV_LOOKUP_TRAIN_CASES = {"even": dict(seed=71, b=2, c=8, d=48, h=8, w=24, iters=3),
+                           "odd": dict(seed=72, b=1, c=8, d=48, h=5, w=7, iters=2)}
+IGEV_LOOKUP_LEAVES = ("fmap1", "fmap2", "geo")
+
+
+def igev_lookup_train_inputs(seed: int, b: int, c: int, d: int, h: int, w: int, iters: int, feat: int = 96,
+                             dtype=torch.float32, device="cpu", requires_grad: bool = True):
+    """Seeded inputs of one training step of IGEV's geometry lookup at a 1/4 plane of h x w over ``iters`` GRU iterations:
+    the geometry encoding volume [b,c,d,h,w] and the two matching-feature maps [b,feat,h,w] -- three leaves that require
+    grad unless ``requires_grad=False`` --, the pixel columns ``coords``, and per iteration a disparity (uniform in
+    [-3, d+3): both borders are crossed), a noise filter [b,d,h,w] and a standard-normal cotangent of the lookup's
+    [b, 2*(9c+9), h, w] output -- none of which requires grad (the reference detaches them)."""
+    def rnd(key, *shape):
+        return torch.randn(*shape, generator=_gen(seed, key))
+
+    def leaf(t):
+        return t.to(device=device, dtype=dtype).requires_grad_(requires_grad)
+
+    def const(t):
+        return t.to(device=device, dtype=dtype)
+    coords = torch.arange(w, dtype=torch.float32).view(1, 1, 1, w).expand(b, 1, h, w).contiguous()
+    return dict(geo=leaf(rnd("geo", b, c, d, h, w)), fmap1=leaf(rnd("fmap1", b, feat, h, w)),
+                fmap2=leaf(rnd("fmap2", b, feat, h, w)), coords=const(coords),
+                disp=[const(torch.rand(b, 1, h, w, generator=_gen(seed, f"disp{i}")) * (d + 6) - 3) for i in range(iters)],
+                noisy=[const(rnd(f"noisy{i}", b, d, h, w)) for i in range(iters)],
+                cot=[const(rnd(f"cot{i}", b, 2 * (9 * c + 9), h, w)) for i in range(iters)])
+
+
+def igev_lookup_train_leaves(x):
+    """The three leaves of ``igev_lookup_train_inputs`` under the names of IGEV_LOOKUP_LEAVES."""
+    return {n: x[n] for n in IGEV_LOOKUP_LEAVES}
+
+
+def igev_lookup_train_step(volume_cls, x):
+    """The lookup side of the reference's training loop (KITTI15/core/igev_stereo_ddim.py:402, :441-443): one
+    ``volume_cls(fmap1, fmap2, geo)`` and T lookups against it, each with its own detached disparity and noise, under a
+    loss that is a linear functional of every lookup: sum_t mean(out_t * cot_t).  Returns (loss, [out_t])."""
+    vol = volume_cls(x["fmap1"], x["fmap2"], x["geo"])
+    outs = [vol(dsp, x["coords"], nz) for dsp, nz in zip(x["disp"], x["noisy"])]
+    loss = 0.0
+    for out, cot in zip(outs, x["cot"]):
+        loss = loss + (out * cot).mean()
+    return loss, outs

@@ -528,6 +528,14 @@ int dv_instance_norm_act_f32(const float* in, float* out, int BC, int HW, float 
  * fmap1 [B,C,H,W1], fmap2 [B,C,H,W2] (C <= 256); corr0 [B,H,W1,W2]; corr1 [B,H,W1,W2/2] (floor). */
 int dv_allpairs_corr_f32(const float* fmap1, const float* fmap2, float* corr0, float* corr1, int B, int C, int H,
                          int W1, int W2, dv_stream_t stream);
+/* Backward of the above for training (the reference differentiates the einsum of geometry_ddim.py:72-80 through the
+ * lookup of every GRU iteration, igev_stereo_ddim.py:441-443).  dcorr0 [B,H,W1,W2] is the TOTAL gradient of corr0: corr1
+ * is only its avg_pool (:28-30) and dv_geo_filter_lookup_bwd_f32 folds that level in.
+ *   dfmap1[b,c,y,x1] = sum_x2 dcorr0[b,y,x1,x2] * fmap2[b,c,y,x2];   dfmap2[b,c,y,x2] = sum_x1 dcorr0[b,y,x1,x2] * fmap1[b,c,y,x1]
+ * dfmap1 [B,C,H,W1] or dfmap2 [B,C,H,W2] may be NULL (not both): that gradient is not computed.  C <= 256.  The sums
+ * over an image width run inside one wave in a fixed order -- no split-K, no atomics: the same bits on every launch. */
+int dv_allpairs_corr_bwd_f32(const float* dcorr0, const float* fmap1, const float* fmap2, float* dfmap1, float* dfmap2,
+                             int B, int C, int H, int W1, int W2, dv_stream_t stream);
 
 /* ---- IGEV: geometry-encoding-volume lookup with the noise filter -----------------------
  * Combined_Geo_Encoding_Volume.__call__ (KITTI15/core/geometry_ddim.py:33-69), 2 pyramid levels,
@@ -539,6 +547,16 @@ int dv_allpairs_corr_f32(const float* fmap1, const float* fmap2, float* corr0, f
 int dv_geo_filter_lookup_f32(const float* geo, const float* corr0, const float* corr1,
                              const float* disp, const float* coords, const float* noisy, float* out,
                              int B, int C, int D, int h, int w, int W2, int radius, dv_stream_t stream);
+/* Backward of the lookup for training (geometry_ddim.py:33-69 differentiated once per GRU iteration of the train loop,
+ * igev_stereo_ddim.py:441-443).  The lookup is linear in the volume and in the correlation rows, so only grad_out
+ * [B,2*(9C+9),h,w], disp, coords and noisy are read -- with the forward's sample positions, zero padding and raw-reshape
+ * noise rows.  dgeo [B,C,D,h,w] and dcorr0 [B,h,w,W2] are caller-allocated; either may be NULL (not both) and is then
+ * skipped.  dcorr0 includes the pooled level's share (corr1 = avg_pool of corr0, :28-30, factor 1/2): feed it to
+ * dv_allpairs_corr_bwd_f32 (geometry_ddim.py:72-80).  Every output element has exactly one writer and is written exactly
+ * once (zero outside the pixel's window): no atomics, no memset needed, the same bits on every launch.  radius 4 only. */
+int dv_geo_filter_lookup_bwd_f32(const float* grad_out, const float* disp, const float* coords, const float* noisy,
+                                 float* dgeo, float* dcorr0, int B, int C, int D, int h, int w, int W2, int radius,
+                                 dv_stream_t stream);
 /* The same lookup FUSED with the 1x1 convolution that consumes it in IGEV's update block (BasicMotionEncoder.convc1 +
  * bias + ReLU, KITTI15/core/update.py:79,:89): out[b, co, y, x] = act(bias[co] + sum_ch w[co, ch] * lookup[b, ch, y, x]),
  * out [B,64,h,w]; the [B,2*(C*9+9),h,w] lookup tensor is never written.  `wpacked` = dv_geo_lookup_conv1x1_pack_weights_f32 of
