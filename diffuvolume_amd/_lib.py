@@ -147,6 +147,9 @@ SIGNATURES = {
     "dv_gru_blend_f32": (c_int, [P, P, P, P, c_size_t, P]),
     "dv_gru_gates_bwd_blend_f32": (c_int, [P, P, P, P, P, P, P, c_size_t, P]),
     "dv_gru_gates_bwd_reset_f32": (c_int, [P, P, P, P, P, c_size_t, P]),
+    "dv_instance_norm_act_bwd_f32": (c_int, [P, P, P, I, I, ctypes.c_float, I, P]),
+    "dv_conv2d_fewin_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I, I, I]),
+    "dv_conv2d_fewin_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P]),
 }
 
 

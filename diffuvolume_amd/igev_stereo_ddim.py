@@ -840,6 +840,17 @@ def _basic_in_train(m, x):
     return F.leaky_relu(x, 0.01) if m.relu else x
 
 
+def _spx_init_train(m, features_left0, stem_2x):
+    """The spx_4 / spx_2 / spx logits (:390-392) on the training route, on the modules of ``m`` (an IGEVUpsampler or the
+    IGEVStereo_ddim itself)."""
+    s4, c = m.spx_4, m.spx_2
+    x = s4[3](s4[2](train2d.conv2d_module(s4[1], _basic_in_train(s4[0], features_left0))))
+    x = _basic_in_train(c.conv1, x)
+    if x.shape != stem_2x.shape:
+        x = F.interpolate(x, size=(stem_2x.shape[-2], stem_2x.shape[-1]), mode="nearest")
+    return train2d.conv_transpose2d_module(m.spx[0], _basic_in_train(c.conv2, torch.cat((x, stem_2x), 1)))
+
+
 class IGEVUpsampler(PlanCache, nn.Module):
     """The upsampling-side modules of IGEVStereo_ddim (:110-112 `spx_2_gru` / `spx_gru`, :104-108 `spx_4` / `spx_2` /
     `spx`) under the reference's attribute names, and the parts of its forward that use them.
@@ -878,12 +889,7 @@ class IGEVUpsampler(PlanCache, nn.Module):
             # (the modules' own forwards take the inference kernels for inputs that ask for no gradient, which would leave
             # these weights without one under a frozen backbone; and MIOpen's backward-weights of these layers does not
             # return the same bits twice, so the convolutions go through train2d like the per-iteration ones)
-            s4, c = self.spx_4, self.spx_2
-            x = s4[3](s4[2](train2d.conv2d_module(s4[1], _basic_in_train(s4[0], features_left0))))
-            x = _basic_in_train(c.conv1, x)
-            if x.shape != stem_2x.shape:
-                x = F.interpolate(x, size=(stem_2x.shape[-2], stem_2x.shape[-1]), mode="nearest")
-            spx_pred = train2d.conv_transpose2d_module(self.spx[0], _basic_in_train(c.conv2, torch.cat((x, stem_2x), 1)))
+            spx_pred = _spx_init_train(self, features_left0, stem_2x)
         else:
             spx_pred = self.spx(self.spx_2(self.spx_4(features_left0), stem_2x))
         return context_upsample(init_disp, spx_pred, scale=4.0, apply_softmax=True).unsqueeze(1)
@@ -1028,6 +1034,218 @@ class Feature(nn.Module):
         return [x4, x8, x16, x32]
 
 
+# ---------------------------------------------------------------------------------------------------
+# The 2-D front: everything IGEVStereo_ddim.forward computes before the cost volume and the GRU loop (:364-377 feature
+# pyramid, stems, matching features; :395-398 context encoder and the GRU's context terms).  `_front2d` is the inference
+# route (what `_front` has always run); `_front2d_train` walks the same modules on the differentiable HIP route:
+# convolutions through train2d.conv2d_any / conv_transpose2d_module, InstanceNorm + activation through
+# train2d.instance_norm_act, BatchNorm2d the module's own call (frozen by `freeze_bn()` an affine map whose weight and bias
+# still train; in train mode batch statistics), ReLU6 / tanh / relu PyTorch.  The modules' own forwards are not used for
+# training: they take the inference kernels whenever the input asks for no gradient -- images never do --, which leaves
+# these weights without one, and their autograd fallback is MIOpen, whose backward-weights does not return the same bits
+# twice.
+# ---------------------------------------------------------------------------------------------------
+def _front2d(m, image1, image2, n_gru_layers):
+    """:364-377 + :395-398 on the modules of ``m`` (an IGEVFront2d or the IGEVStereo_ddim itself), inference kernels ->
+    (features_left, stem_2x, match_left, match_right, net_list, inp_list)."""
+    image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
+    image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
+    features_left, features_right = m.feature(image1), m.feature(image2)
+    stem_2x = hip_sequential(m.stem_2, image1)
+    stem_4x = hip_sequential(m.stem_4, stem_2x)
+    stem_4y = hip_sequential(m.stem_4, hip_sequential(m.stem_2, image2))
+    features_left[0] = torch.cat((features_left[0], stem_4x), 1)
+    features_right[0] = torch.cat((features_right[0], stem_4y), 1)
+    match_left = hip_conv2d(m.desc, m.conv(features_left[0])).contiguous()
+    match_right = hip_conv2d(m.desc, m.conv(features_right[0])).contiguous()
+    cnet_list = m.cnet(image1, num_layers=n_gru_layers)
+    net_list = [torch.tanh(x[0]) for x in cnet_list]
+    inp_list = [torch.relu(x[1]) for x in cnet_list]
+    inp_list = [list(hip_conv2d(conv, i).split(split_size=conv.out_channels // 3, dim=1))
+                for i, conv in zip(inp_list, m.context_zqr_convs)]
+    inp_list = [[t.contiguous() for t in trio] for trio in inp_list]
+    return features_left, stem_2x, match_left, match_right, net_list, inp_list
+
+
+def _norm_act_train(mods, j, x):
+    """The [BatchNorm2d | InstanceNorm2d][ReLU | ReLU6 | LeakyReLU] members that follow a convolution at ``mods[j]`` ->
+    (x, index of the first member not consumed)."""
+    inorm = None
+    if j < len(mods) and isinstance(mods[j], nn.BatchNorm2d):
+        x, j = mods[j](x), j + 1
+    elif j < len(mods) and isinstance(mods[j], nn.InstanceNorm2d):
+        inorm, j = mods[j], j + 1
+        if inorm.affine or inorm.track_running_stats:
+            raise _lib.DiffuVolumeError("InstanceNorm2d on the HIP front: affine=False, no running statistics")
+    a = mods[j] if j < len(mods) and isinstance(mods[j], (nn.ReLU, nn.ReLU6, nn.LeakyReLU)) else None
+    if isinstance(a, nn.LeakyReLU) and abs(a.negative_slope - 0.01) > 1e-12:
+        raise _lib.DiffuVolumeError("LeakyReLU on the HIP front: negative_slope 0.01")
+    if inorm is not None:                                      # ReLU / LeakyReLU fused into the norm's launch, ReLU6 after it
+        fused = ACT_NONE if a is None or isinstance(a, nn.ReLU6) else (ACT_LEAKY if isinstance(a, nn.LeakyReLU) else ACT_RELU)
+        x = train2d.instance_norm_act(x, fused, inorm.eps)
+        if isinstance(a, nn.ReLU6):
+            x = F.relu6(x)
+    elif a is not None:
+        x = F.relu6(x) if isinstance(a, nn.ReLU6) else (F.leaky_relu(x, 0.01) if isinstance(a, nn.LeakyReLU) else F.relu(x))
+    return x, j + (a is not None)
+
+
+def _basic_in_front_train(m, x):
+    """A 2-D BasicConv_IN of the front on the training route: convolution, InstanceNorm + LeakyReLU one launch each way."""
+    x = train2d.conv_transpose2d_module(m.conv, x) if isinstance(m.conv, nn.ConvTranspose2d) else train2d.conv2d_any(m.conv, x)
+    if m.use_in:
+        return train2d.instance_norm_act(x, ACT_LEAKY if m.relu else ACT_NONE, m.IN.eps)
+    return F.leaky_relu(x, 0.01) if m.relu else x
+
+
+def _residual_train(m, x):
+    """ResidualBlock.forward (core/extractor.py:46-56) on the training route."""
+    y = F.relu(m.norm1(train2d.conv2d_any(m.conv1, x)))
+    y = F.relu(m.norm2(train2d.conv2d_any(m.conv2, y)))
+    if m.downsample is not None:
+        x = m.downsample[1](train2d.conv2d_any(m.downsample[0], x))
+    return F.relu(x + y)
+
+
+def _conv2x_in_train(m, x, rem):
+    """Conv2x_IN.forward (core/submodule.py:133-150) on the training route."""
+    x = _basic_in_front_train(m.conv1, x)
+    if x.shape != rem.shape:
+        x = F.interpolate(x, size=(rem.shape[-2], rem.shape[-1]), mode="nearest")
+    x = torch.cat((x, rem), 1) if m.concat else x + rem
+    return _basic_in_front_train(m.conv2, x)
+
+
+def train_sequential(seq, x: torch.Tensor) -> torch.Tensor:
+    """`hip_sequential`'s walk on the training route: [conv][BatchNorm2d | InstanceNorm2d][ReLU | ReLU6 | LeakyReLU(0.01)]
+    groups, nested nn.Sequential, ResidualBlock and BasicConv_IN.  A member without a training route raises."""
+    mods = list(seq) if isinstance(seq, (nn.Sequential, list, tuple)) else [seq]
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.ConvTranspose2d):
+            x, i = _norm_act_train(mods, i + 1, train2d.conv_transpose2d_module(m, x))
+        elif isinstance(m, nn.Conv2d):
+            x, i = _norm_act_train(mods, i + 1, train2d.conv2d_any(m, x))
+        elif isinstance(m, nn.Sequential):
+            x, i = train_sequential(m, x), i + 1
+        elif isinstance(m, ResidualBlock):
+            x, i = _residual_train(m, x), i + 1
+        elif isinstance(m, BasicConv_IN):
+            x, i = _basic_in_front_train(m, x), i + 1
+        elif isinstance(m, (nn.Identity, nn.Dropout, nn.Dropout2d)):
+            x, i = m(x), i + 1
+        else:
+            raise _lib.DiffuVolumeError(f"the 2-D front has no training route for {type(m).__name__}")
+    return x
+
+
+def _feature_train(m, x):
+    """Feature.forward (core/extractor.py:337-361) on the training route.  A backbone that is not made of plain
+    [Conv2d, BatchNorm2d, ReLU / ReLU6] stages (timm's MobileNetV2), or a feature module of another class, is called as
+    is: the injected module's own business."""
+    if not isinstance(m, Feature):
+        return m(x)
+    if m._backbone_on_hip():
+        x2 = train_sequential(m.block0, train_sequential([m.conv_stem, m.bn1, m.act1], x))
+        x4 = train_sequential(m.block1, x2)
+        x8 = train_sequential(m.block2, x4)
+        x16 = train_sequential(m.block3, x8)
+        x32 = train_sequential(m.block4, x16)
+    else:
+        x2 = m.block0(m.act1(m.bn1(m.conv_stem(x))))
+        x4 = m.block1(x2)
+        x8 = m.block2(x4)
+        x16 = m.block3(x8)
+        x32 = m.block4(x16)
+    x16 = _conv2x_in_train(m.deconv32_16, x32, x16)
+    x8 = _conv2x_in_train(m.deconv16_8, x16, x8)
+    x4 = _basic_in_front_train(m.conv4, _conv2x_in_train(m.deconv8_4, x8, x4))
+    return [x4, x8, x16, x32]
+
+
+def _cnet_train(m, x, num_layers):
+    """MultiBasicEncoder.forward (core/extractor.py:258-295, dual_inp=False) on the training route."""
+    if not isinstance(m, MultiBasicEncoder):
+        return m(x, num_layers=num_layers)
+    x = F.relu(m.norm1(train2d.conv2d_any(m.conv1, x)))
+    x = train_sequential([m.layer1, m.layer2, m.layer3], x)
+    outs = ([train_sequential(f, x) for f in m.outputs04],)
+    if num_layers >= 2:
+        y = train_sequential(m.layer4, x)
+        outs += ([train_sequential(f, y) for f in m.outputs08],)
+    if num_layers >= 3:
+        z = train_sequential(m.layer5, y)
+        outs += ([train_sequential(f, z) for f in m.outputs16],)
+    return outs
+
+
+def _front2d_train(m, image1, image2, n_gru_layers):
+    """`_front2d` on the training route (train mode with autograd recording)."""
+    for name, t in (("image1", image1), ("image2", image2)):
+        if not t.is_cuda:
+            raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
+    if torch.is_autocast_enabled("cuda"):
+        raise _lib.DiffuVolumeError("the 2-D front trains in float32: fp16 / bf16 autocast is not supported in train mode "
+                                    "(mixed-precision training is not implemented)")
+    image1 = (2 * (image1.float() / 255.0) - 1.0).contiguous()
+    image2 = (2 * (image2.float() / 255.0) - 1.0).contiguous()
+    features_left, features_right = _feature_train(m.feature, image1), _feature_train(m.feature, image2)
+    stem_2x = train_sequential(m.stem_2, image1)
+    stem_4x = train_sequential(m.stem_4, stem_2x)
+    stem_4y = train_sequential(m.stem_4, train_sequential(m.stem_2, image2))
+    features_left[0] = torch.cat((features_left[0], stem_4x), 1)
+    features_right[0] = torch.cat((features_right[0], stem_4y), 1)
+    match_left = train2d.conv2d_any(m.desc, _basic_in_front_train(m.conv, features_left[0])).contiguous()
+    match_right = train2d.conv2d_any(m.desc, _basic_in_front_train(m.conv, features_right[0])).contiguous()
+    cnet_list = _cnet_train(m.cnet, image1, n_gru_layers)
+    net_list = [torch.tanh(x[0]) for x in cnet_list]
+    inp_list = [torch.relu(x[1]) for x in cnet_list]
+    inp_list = [list(train2d.conv2d_any(conv, i).split(split_size=conv.out_channels // 3, dim=1))
+                for i, conv in zip(inp_list, m.context_zqr_convs)]
+    inp_list = [[t.contiguous() for t in trio] for trio in inp_list]
+    return features_left, stem_2x, match_left, match_right, net_list, inp_list
+
+
+class IGEVFront2d(PlanCache, nn.Module):
+    """The 2-D front's modules of IGEVStereo_ddim (:180-194 `feature`, `stem_2`, `stem_4`, `conv`, `desc`; :163-170 `cnet`,
+    `context_zqr_convs`) under the reference's attribute names, and the parts of its forward that use them (:364-377,
+    :395-398).  ``forward(image1, image2)`` (images in 0..255) returns ``(features_left, stem_2x, match_left, match_right,
+    net_list, inp_list)``.  In eval mode (or under no_grad) it runs the inference kernels, the bits of
+    IGEVStereo_ddim's own front; in train mode with autograd recording every layer is differentiable on the HIP kernels
+    (see ``_front2d_train``).  ``feature``: ``Feature(backbone)``, as for IGEVStereo_ddim."""
+
+    def __init__(self, args, feature: nn.Module, cnet: Optional[nn.Module] = None):
+        super().__init__()
+        self.args = args
+        hidden = list(args.hidden_dims)
+        self.cnet = cnet if cnet is not None else MultiBasicEncoder(output_dim=[hidden, hidden], norm_fn="batch",
+                                                                    downsample=args.n_downsample)
+        self.context_zqr_convs = nn.ModuleList([nn.Conv2d(hidden[i], hidden[i] * 3, 3, padding=1)
+                                                for i in range(args.n_gru_layers)])
+        self.feature = feature
+        self.stem_2, self.stem_4 = _stem(3, 32), _stem(32, 48)
+        self.conv = BasicConv_IN(96, 96, kernel_size=3, padding=1, stride=1)
+        self.desc = nn.Conv2d(96, 96, kernel_size=1, padding=0, stride=1)
+
+    def _build_plans(self, slot):
+        return {}                   # the front's inference plans live per layer (`hip_conv2d`), training builds them per call
+
+    def freeze_bn(self):
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+
+    def forward(self, image1, image2):
+        run = _front2d_train if _train_mode(self) else _front2d
+        return run(self, image1, image2, self.args.n_gru_layers)
+
+
+def _stem(cin, cout):
+    return nn.Sequential(BasicConv_IN(cin, cout, kernel_size=3, stride=2, padding=1),
+                         nn.Conv2d(cout, cout, 3, 1, 1, bias=False), nn.InstanceNorm2d(cout), nn.ReLU())
+
+
 class IGEVStereo_ddim(PlanCache, nn.Module):
     """``IGEVStereo_ddim(args).forward(image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False)
     -> (pred, pred)`` (eval path, igev_stereo_ddim.py:361-427).  ``args``: hidden_dims, n_gru_layers, n_downsample,
@@ -1038,7 +1256,9 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
     ``feature``: the MobileNetV2 feature pyramid (``Feature(backbone)``); None = the reference's own construction from
     timm's pretrained ``mobilenetv2_100`` (core/extractor.py:327-335), which needs ``timm`` to be importable;
     ``cnet``: optional replacement for the context encoder.  ``sampling_timesteps`` / ``ensemble_cof`` are
-    hard-coded to 2 / [0.6, 0.1, 0.3] in the reference (:124, :353); BASELINE config 5 asks for 20 steps."""
+    hard-coded to 2 / [0.6, 0.1, 0.3] in the reference (:124, :353); BASELINE config 5 asks for 20 steps.
+    Training: ``forward`` refuses train mode; ``forward_train`` is the reference's train branch (:364-463) on the
+    differentiable HIP routes and returns ``(init_disp, disp_preds)`` for ``loss.sequence_loss``."""
 
     def __init__(self, args, feature: Optional[nn.Module] = None, cnet: Optional[nn.Module] = None,
                  sampling_timesteps: int = 2, ensemble_cof: Optional[Sequence[float]] = None):
@@ -1171,27 +1391,81 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
     def _front(self, image1, image2):
         """:364-400 up to the GRU inputs: feature pyramid + stems, matching features, cost volume + initial disparity,
         context encoder, geometry lookup object.  Shared with the origin network (igev_stereo.py:151-194)."""
-        image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
-        image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
-        features_left, features_right = self.feature(image1), self.feature(image2)
-        stem_2x = hip_sequential(self.stem_2, image1)
-        stem_4x = hip_sequential(self.stem_4, stem_2x)
-        stem_4y = hip_sequential(self.stem_4, hip_sequential(self.stem_2, image2))
-        features_left[0] = torch.cat((features_left[0], stem_4x), 1)
-        features_right[0] = torch.cat((features_right[0], stem_4y), 1)
-        match_left = hip_conv2d(self.desc, self.conv(features_left[0])).contiguous()
-        match_right = hip_conv2d(self.desc, self.conv(features_right[0])).contiguous()
+        features_left, stem_2x, match_left, match_right, net_list, inp_list = _front2d(self, image1, image2,
+                                                                                        self.args.n_gru_layers)
         geo, init_disp = self.cost_volume(match_left, match_right, features_left)
-        cnet_list = self.cnet(image1, num_layers=self.args.n_gru_layers)
-        net_list = [torch.tanh(x[0]) for x in cnet_list]
-        inp_list = [torch.relu(x[1]) for x in cnet_list]
-        inp_list = [list(hip_conv2d(conv, i).split(split_size=conv.out_channels // 3, dim=1))
-                    for i, conv in zip(inp_list, self.context_zqr_convs)]
-        inp_list = [[t.contiguous() for t in trio] for trio in inp_list]
         from .geometry_ddim import Combined_Geo_Encoding_Volume
         geo_fn = Combined_Geo_Encoding_Volume(match_left, match_right, geo, radius=self.args.corr_radius,
                                               num_levels=self.args.corr_levels)
         return features_left, stem_2x, init_disp, net_list, inp_list, geo_fn
+
+    def q_sample(self, x_start, t, noise=None):
+        """:213-218 with ``t`` of shape [1] (one draw for the batch, :430)."""
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        return self.sqrt_alphas_cumprod[t].reshape(-1, 1, 1, 1) * x_start + \
+            self.sqrt_one_minus_alphas_cumprod[t].reshape(-1, 1, 1, 1) * noise
+
+    def forward_train(self, image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False, *, t=None,
+                      noise=None):
+        """The reference's train branch (:364-463) -> ``(init_disp [B,1,H,W], disp_preds: iters x [B,1,H,W])``, what
+        train_stereo.py:160-163 feeds to ``sequence_loss``; ``disp_up`` of the last iteration under ``test_mode``.  Every
+        stage runs on its differentiable HIP route: the 2-D front (``_front2d_train``), the cost volume, the spx heads, the
+        geometry lookup, the update block and the convex upsampling.  ``flow_gt``: the quarter-resolution origin disparity
+        [B,1,h,w] that is two-hot encoded and diffused (:405-432); ``flow_full`` is unused, as in the reference's train
+        branch.  ``t`` ([1], long) / ``noise`` ([B,48,h,w]): the diffusion step and the q_sample noise, by default the
+        reference's draws ``torch.randint(0, 1000, (1,))`` and ``randn_like``.  The noisy volume is detached like :436, so
+        `time_embedding` gets no gradient, as in the reference."""
+        if not self.training:
+            raise _lib.DiffuVolumeError("forward_train is the training entry (model.train()); forward is the eval one")
+        if not torch.is_grad_enabled():
+            raise _lib.DiffuVolumeError("forward_train under no_grad: validation runs model.eval() and forward")
+        if getattr(self.args, "mixed_precision", False) or torch.is_autocast_enabled("cuda"):
+            raise _lib.DiffuVolumeError("IGEVStereo_ddim trains in float32: args.mixed_precision / fp16 / bf16 autocast are "
+                                        "not supported in train mode (mixed-precision training is not implemented)")
+        if flow_init is not None:
+            raise _lib.DiffuVolumeError("flow_init: the reference's train branch does not read it (:441-457)")
+        for name, ten in (("image1", image1), ("image2", image2), ("flow_gt", flow_gt)):
+            if not ten.is_cuda:
+                raise _lib.DiffuVolumeError(f"{name} is on {ten.device}: training runs on the MI355X (no CPU fallback)")
+        n_layers = self.args.n_gru_layers
+        features_left, stem_2x, match_left, match_right, net_list, inp_list = _front2d_train(self, image1, image2, n_layers)
+        geo, init_disp = self.cost_volume(match_left, match_right, features_left)
+        spx_pred = None if test_mode else _spx_init_train(self, features_left[0], stem_2x)
+        from .geometry_ddim import Combined_Geo_Encoding_Volume
+        geo_fn = Combined_Geo_Encoding_Volume(match_left, match_right, geo, radius=self.args.corr_radius,
+                                              num_levels=self.args.corr_levels)
+        b, _, h, w = match_left.shape
+        dev = match_left.device
+        with torch.no_grad():                                                           # :402-436
+            coords = torch.arange(w, dtype=torch.float32, device=dev).reshape(1, 1, 1, w).repeat(b, 1, h, 1)
+            x0 = self.encode_disparity(flow_gt)
+            if tuple(x0.shape) != (b, 48, h, w):
+                raise RuntimeError(f"flow_gt must be the quarter-resolution disparity [B,1,{h},{w}], got {tuple(flow_gt.shape)}")
+            t = torch.randint(0, self.num_timesteps, (1,), device=dev).long() if t is None else t.to(dev).long().reshape(1)
+            noisy = self.q_sample(x0, t, None if noise is None else noise.to(device=dev, dtype=torch.float32))
+            noisy = self.time_embedding(noisy, t)
+            noisy = noisy + t.reshape(1, 1, 1, 1) / self.num_timesteps
+            noisy = torch.clamp(noisy, min=-1 * self.scale, max=self.scale)
+            noisy = (((noisy / self.scale) + 1) / 2.).float().contiguous()
+        disp, disp_preds, disp_up = init_disp, [], None
+        for itr in range(iters):                                                        # :441-457
+            disp = disp.detach()
+            geo_feat = geo_fn(disp, coords, noisy)
+            if n_layers == 3 and self.args.slow_fast_gru:
+                net_list = self.update_block(net_list, inp_list, iter16=True, iter08=False, iter04=False, update=False)
+            if n_layers >= 2 and self.args.slow_fast_gru:
+                net_list = self.update_block(net_list, inp_list, iter16=n_layers == 3, iter08=True, iter04=False, update=False)
+            net_list, mask_feat_4, delta_disp = self.update_block(net_list, inp_list, geo_feat, disp, iter16=n_layers == 3,
+                                                                  iter08=n_layers >= 2)
+            disp = disp + delta_disp
+            if test_mode and itr < iters - 1:
+                continue
+            disp_up = self.upsample_disp(disp, mask_feat_4, stem_2x)
+            disp_preds.append(disp_up)
+        if test_mode:
+            return disp_up
+        return context_upsample(init_disp, spx_pred, scale=4.0, apply_softmax=True).unsqueeze(1), disp_preds       # :462
 
     def forward(self, image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False, noise=None):
         if self.training:

@@ -33,3 +33,25 @@ def model_loss_test(disp_ests, disp_gt, mask):
 def model_loss_kitti12(disp_ests, disp_gt, mask):
     """KITTI12/models/loss.py ``model_loss``: the six predictions of PWCNet_ddim's training branch."""
     return _weighted(disp_ests, disp_gt, mask, [0.5, 0.5, 0.5, 0.7, 1.0, 1.3], F.smooth_l1_loss)
+
+
+def sequence_loss(disp_preds, disp_init_pred, disp_gt, valid, loss_gamma: float = 0.9, max_disp: int = 192):
+    """KITTI15/train_stereo.py:33-62: smooth-L1 of the initial disparity plus the exponentially weighted L1 of every GRU
+    iteration's prediction over the valid pixels -> (loss, metrics).  ``disp_preds``: the list `forward_train` returns,
+    ``disp_gt`` [B,1,H,W], ``valid`` [B,H,W].  (A single prediction gets weight 1: the reference divides by zero there.)"""
+    n = len(disp_preds)
+    assert n >= 1
+    mag = torch.sum(disp_gt ** 2, dim=1).sqrt()
+    valid = ((valid >= 0.5) & (mag < max_disp)).unsqueeze(1)
+    assert valid.shape == disp_gt.shape, [valid.shape, disp_gt.shape]
+    assert not torch.isinf(disp_gt[valid]).any()
+    loss = 1.0 * F.smooth_l1_loss(disp_init_pred[valid], disp_gt[valid], reduction="mean")
+    gamma = loss_gamma ** (15 / (n - 1)) if n > 1 else 1.0
+    for i, pred in enumerate(disp_preds):
+        i_loss = (pred - disp_gt).abs()
+        assert i_loss.shape == valid.shape, [i_loss.shape, valid.shape, disp_gt.shape, pred.shape]
+        loss = loss + gamma ** (n - i - 1) * i_loss[valid].mean()
+    epe = torch.sum((disp_preds[-1] - disp_gt) ** 2, dim=1).sqrt().view(-1)[valid.view(-1)]
+    metrics = {"epe": epe.mean().item(), "1px": (epe < 1).float().mean().item(), "3px": (epe < 3).float().mean().item(),
+               "5px": (epe < 5).float().mean().item()}
+    return loss, metrics

@@ -369,3 +369,61 @@ def igev_lookup_train_step(volume_cls, x):
     for out, cot in zip(outs, x["cot"]):
         loss = loss + (out * cot).mean()
     return loss, outs
+
+
+# ---- IGEV: the 2-D front and the whole training step (tools/make_golden_igev_front_train.py, ..._train_step.py) -------
+IGEV_TRAIN_ARGS = dict(hidden_dims=[128, 128, 128], n_gru_layers=3, n_downsample=2, corr_levels=2, corr_radius=4,
+                       slow_fast_gru=False, max_disp=192, mixed_precision=False, corr_implementation="reg",
+                       shared_backbone=False)
+IGEV_TRAIN_WEIGHT_SEED = 55
+IGEV_FRONT_TRAIN_CASES = {"b1": dict(seed=109, b=1, h=32, w=64), "b2": dict(seed=426, b=2, h=32, w=64)}
+IGEV_FRONT_MODULES = ("feature", "stem_2", "stem_4", "conv", "desc", "cnet", "context_zqr_convs")
+IGEV_TRAIN_STEP_CASE = dict(seed=83, b=2, h=64, w=128, iters=3, t=400)
+
+
+def igev_train_images(seed: int, b: int, h: int, w: int, dtype=torch.float32, device="cpu"):
+    """A stereo pair in 0..255: random texture, the right image the left shifted by 6 pixels."""
+    img1 = torch.rand(b, 3, h, w, generator=_gen(seed, "image1")) * 255
+    return img1.to(device=device, dtype=dtype), torch.roll(img1, -6, dims=-1).to(device=device, dtype=dtype)
+
+
+def igev_front_flat(out):
+    """The outputs of the 2-D front (features_left, stem_2x, match_left, match_right, net_list, inp_list) as one list."""
+    features_left, stem_2x, match_left, match_right, net_list, inp_list = out
+    return [*features_left, stem_2x, match_left, match_right, *net_list, *(t for trio in inp_list for t in trio)]
+
+
+def igev_front_train_loss(out, seed: int):
+    """sum_i mean(out_i * cot_i) with seeded cotangents over every output of the front: a smooth loss."""
+    loss = 0.0
+    for i, t in enumerate(igev_front_flat(out)):
+        cot = torch.randn(tuple(t.shape), generator=_gen(seed, f"cot{i}")).to(device=t.device, dtype=t.dtype)
+        loss = loss + (t * cot).mean()
+    return loss
+
+
+def igev_train_step_inputs(seed: int, b: int, h: int, w: int, iters: int, t: int, dtype=torch.float32, device="cpu"):
+    """Images, the full-resolution disparity and its quarter-resolution form, the valid mask, and the fixed draws of the
+    train branch: the diffusion step ``t`` [1] and the q_sample noise [B,48,h/4,w/4]."""
+    import torch.nn.functional as F
+    img1, img2 = igev_train_images(seed, b, h, w, dtype, device)
+    g = _gen(seed, "disp")
+    flow_full = (6 + torch.randn(b, 1, h, w, generator=g)).clamp(0.5, 47)
+    flow_gt = F.interpolate(flow_full, size=(h // 4, w // 4), mode="bilinear") / 4
+    valid = (torch.rand(b, h, w, generator=g) > 0.1).float()
+    noise = torch.randn(b, 48, h // 4, w // 4, generator=_gen(seed, "noise"))
+    return dict(image1=img1, image2=img2, flow_full=flow_full.to(device=device, dtype=dtype),
+                flow_gt=flow_gt.to(device=device, dtype=dtype), valid=valid.to(device),
+                noise=noise.to(device=device, dtype=dtype), t=torch.tensor([t], dtype=torch.long, device=device),
+                iters=iters)
+
+
+def igev_sequence_loss_inputs(seed: int, b: int = 2, h: int = 16, w: int = 24, n: int = 3, dtype=torch.float32):
+    """Seeded arguments of ``sequence_loss``: n predictions and the initial one around a ground truth that has pixels
+    beyond max_disp and invalid ones, and errors on both sides of smooth-L1's knee."""
+    g = _gen(seed, "sequence_loss")
+    gt = torch.rand(b, 1, h, w, generator=g) * 230
+    valid = (torch.rand(b, h, w, generator=g) > 0.2).float()
+    preds = [(gt + torch.randn(b, 1, h, w, generator=g) * (3.0 / (i + 1))).to(dtype) for i in range(n)]
+    init = (gt + torch.randn(b, 1, h, w, generator=g) * 1.5).to(dtype)
+    return preds, init, gt.to(dtype), valid

@@ -26,8 +26,14 @@ IGEV's convex-upsampling head (``igev_stereo_ddim.IGEVUpsampler`` in train mode)
 ``conv_transpose2d_k4`` / ``conv_transpose2d_module``, a ConvTranspose2d(kernel 4, stride 2, padding 1) whose forward is
 ``Deconv2dK4S2Plan``'s (four parity 3x3 convolutions + pixel shuffle), whose input gradient is ONE 3x3 forward launch on
 the pixel-unshuffled output gradient with the flipped parity weights (``TrainDeconvPlan``, packed once per plan) and
-whose weight gradient is ``dv_deconv2d_k4s2_wgrad_f32`` (csrc/deconv2d_k4_bwd.hip).  Every other 2-D convolution of the
-training graphs keeps PyTorch autograd."""
+whose weight gradient is ``dv_deconv2d_k4s2_wgrad_f32`` (csrc/deconv2d_k4_bwd.hip).
+
+IGEV's once-per-pair 2-D front (``igev_stereo_ddim.IGEVFront2d`` / ``IGEVStereo_ddim.forward_train``) uses the fourth
+part: ``conv2d_s2`` (3x3, stride 2: forward on ``Conv2dPlan(stride=2)``, both gradients on the k4 transposed-convolution
+kernels above through an exact identity), ``conv2d_k1s2`` (the 1x1 stride-2 ``downsample``), ``conv2d_fewin`` (the image
+convolutions: weight gradient on ``dv_conv2d_fewin_wgrad_f32``, no input gradient), ``instance_norm_act`` (backward on
+``dv_instance_norm_act_bwd_f32``, both csrc/igev_front_bwd.hip) and the dispatcher ``conv2d_any``.  Plans are built per
+call: these layers run once per pair."""
 from __future__ import annotations
 
 import os
@@ -37,7 +43,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan, Deconv2dK4S2Plan
+from .submodule import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan, Deconv2dK4S2Plan
 from .train3d import _check
 
 
@@ -480,3 +486,197 @@ def conv_transpose2d_module(m: torch.nn.ConvTranspose2d, x: torch.Tensor, plan=N
         raise _lib.DiffuVolumeError(f"conv_transpose2d_module: kernel 4, stride 2, padding 1, no output padding, "
                                     f"groups 1 only, got {m}")
     return conv_transpose2d_k4(x, m.weight, m.bias, plan)
+
+
+# ---- IGEV's once-per-pair 2-D front: stride-2 and few-input-channel convolutions, InstanceNorm + activation -----------
+
+def _embed_k4(w: torch.Tensor) -> torch.Tensor:
+    """A [Cout,Cin,3,3] convolution weight as the [in = Cout, out = Cin, 4, 4] weight of the transposed convolution that is
+    the stride-2 convolution's adjoint: the 3x3 taps top-left, a zero last row and column."""
+    return F.pad(w.detach(), (0, 1, 0, 1)).contiguous()
+
+
+class Conv2dS2Fn(torch.autograd.Function):
+    """conv2d(x, weight, bias, stride 2, padding 1) for a 3x3 kernel.  Forward: ``Conv2dPlan(stride=2)``.  The backward
+    needs no kernel of its own: output pixel (i, j) reads input pixel (2i - 1 + ky, 2j - 1 + kx), which is the index map
+    of ConvTranspose2d(4, stride 2, padding 1) restricted to ky, kx < 3.  So, with the filter embedded in a 4x4 one,
+      * dx = conv_transpose2d_k4(g, w4) cropped to H x W (``Deconv2dK4S2Plan``: [Cout,Cin,3,3] is already its [in,out]
+        layout);
+      * dw = dv_deconv2d_k4s2_wgrad_f32 with the roles swapped (x := g, g := x zero-padded to 2Ho x 2Wo), [:, :, :3, :3].
+    Both are exact (the fourth row / column multiplies zeros or is dropped)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _check(x, "x")
+        _check(weight, "weight")
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[1]:
+            raise _lib.DiffuVolumeError(f"conv2d_s2: x {tuple(x.shape)} against weight {tuple(weight.shape)} (3x3 only)")
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        b = None if bias is None else bias.detach()
+        return Conv2dPlan(weight.detach().contiguous(), None, act=ACT_NONE, bias=b, stride=2)(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        h, wd = x.shape[2:]
+        ho, wo = g.shape[2:]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = Deconv2dK4S2Plan(_embed_k4(w), None)(g)[:, :, :h, :wd]
+        if ctx.needs_input_grad[1]:
+            xp = x if (h, wd) == (2 * ho, 2 * wo) else F.pad(x, (0, 2 * wo - wd, 0, 2 * ho - h))    # odd H or W only
+            dw = deconv2d_k4_weight_grad(g, xp)[:, :, :3, :3].contiguous()
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = g.sum(dim=(0, 2, 3))
+        return dx, dw, db
+
+
+def conv2d_s2(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, weight, bias, stride=2, padding=1) for a 3x3 kernel on the training route."""
+    if route() == "torch":
+        return F.conv2d(x, weight, bias, stride=2, padding=1)
+    return Conv2dS2Fn.apply(x, weight, bias)
+
+
+def conv2d_k1s2(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, weight, bias, stride=2) for a 1x1 kernel (the `downsample` of ResidualBlock, core/extractor.py:40-44):
+    the stride-1 function on every second row and column."""
+    if route() == "torch":
+        return F.conv2d(x, weight, bias, stride=2)
+    _check(x, "x")
+    return Conv2dFn.apply(x[:, :, ::2, ::2].contiguous(), weight, bias, 1)
+
+
+def conv2d_fewin_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int) -> torch.Tensor:
+    """dW [Cout,Cin,k,k] of a convolution with <= 4 input channels (k in {3,5,7}, stride in {1,2}, padding k/2) with input
+    ``x`` and output gradient ``g``."""
+    _check(x, "x")
+    _check(g, "output gradient")
+    x, g = x.contiguous(), g.contiguous()
+    b, cin, h, w = x.shape
+    cout = g.shape[1]
+    if g.shape[0] != b or tuple(g.shape[2:]) != ((h - 1) // stride + 1, (w - 1) // stride + 1):
+        raise _lib.DiffuVolumeError(f"conv2d_fewin_weight_grad: x {tuple(x.shape)} against g {tuple(g.shape)}, stride {stride}")
+    lib = _lib.load()
+    n = lib.dv_conv2d_fewin_wgrad_workspace_floats(b, cin, h, w, cout, k, stride)
+    if n == 0:
+        raise _lib.DiffuVolumeError(f"dv_conv2d_fewin_wgrad_f32 does not take Cin={cin} k={k} stride={stride}")
+    dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dv_conv2d_fewin_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
+                                                 cout, k, stride, _lib.stream_ptr()), "dv_conv2d_fewin_wgrad_f32")
+    return dw
+
+
+class Conv2dFewInFn(torch.autograd.Function):
+    """A convolution of an IMAGE (<= 4 channels; k in {3,5,7}, stride in {1,2}, padding k/2): forward on
+    ``dv_conv2d_fewin_f32`` (the inference kernel), weight gradient on ``dv_conv2d_fewin_wgrad_f32``.  Images are data:
+    there is no input gradient, and an input that asks for one is refused."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        _check(x, "x")
+        _check(weight, "weight")
+        k = int(weight.shape[-1])
+        if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1] or weight.shape[1] > 4 or \
+                tuple(weight.shape[2:]) != (k, k) or k not in (3, 5, 7) or stride not in (1, 2):
+            raise _lib.DiffuVolumeError(f"conv2d_fewin: x {tuple(x.shape)}, weight {tuple(weight.shape)}, stride {stride}")
+        x, wt = x.contiguous(), weight.detach().contiguous()
+        b, cin, h, w = x.shape
+        out = torch.empty((b, wt.shape[0], (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dv_conv2d_fewin_f32(x.data_ptr(), wt.data_ptr(), _lib.ptr(None if bias is None else bias.detach()),
+                                                       0, 0, out.data_ptr(), b, cin, h, w, wt.shape[0], k, stride, ACT_NONE,
+                                                       _lib.stream_ptr()), "dv_conv2d_fewin_f32")
+        ctx.save_for_backward(x)
+        ctx.k, ctx.stride, ctx.has_bias = k, stride, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = g.contiguous()
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            dw = conv2d_fewin_weight_grad(x, g, ctx.k, ctx.stride)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = g.sum(dim=(0, 2, 3))
+        return None, dw, db, None
+
+
+def conv2d_fewin(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1) -> torch.Tensor:
+    """F.conv2d(x, weight, bias, stride, padding=k//2) of an image (<= 4 channels) on the training route."""
+    if x.requires_grad:
+        raise _lib.DiffuVolumeError("conv2d_fewin: the input is an image (data); it has no input gradient")
+    if route() == "torch":
+        return F.conv2d(x, weight, bias, stride=stride, padding=weight.shape[-1] // 2)
+    return Conv2dFewInFn.apply(x, weight, bias, stride)
+
+
+class InstanceNormActFn(torch.autograd.Function):
+    """nn.InstanceNorm2d (affine=False) + activation: the forward is the inference launch out of place (its bits), the
+    backward ``dv_instance_norm_act_bwd_f32`` on the saved pre-norm tensor."""
+
+    @staticmethod
+    def forward(ctx, x, act, eps):
+        _check(x, "x")
+        x = x.contiguous()
+        b, c, h, w = x.shape
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dv_instance_norm_act_f32(x.data_ptr(), out.data_ptr(), b * c, h * w, float(eps), act,
+                                                            _lib.stream_ptr()), "dv_instance_norm_act_f32")
+        ctx.save_for_backward(x)
+        ctx.act, ctx.eps = act, float(eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = g.contiguous()
+        b, c, h, w = x.shape
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dv_instance_norm_act_bwd_f32(x.data_ptr(), g.data_ptr(), dx.data_ptr(), b * c, h * w,
+                                                                ctx.eps, ctx.act, _lib.stream_ptr()),
+                       "dv_instance_norm_act_bwd_f32")
+        return dx, None, None
+
+
+def instance_norm_act(x: torch.Tensor, act: int = ACT_NONE, eps: float = 1e-5) -> torch.Tensor:
+    """act(F.instance_norm(x, eps=eps)) for act in {ACT_NONE, ACT_RELU, ACT_LEAKY} on the training route."""
+    if act not in (ACT_NONE, ACT_RELU, ACT_LEAKY):
+        raise _lib.DiffuVolumeError(f"instance_norm_act: none, ReLU or LeakyReLU(0.01) only, got activation {act}")
+    if x.dim() != 4:
+        raise _lib.DiffuVolumeError(f"instance_norm_act: a [B,C,H,W] tensor, got {tuple(x.shape)}")
+    if route() == "torch":
+        y = F.instance_norm(x, eps=eps)
+        return y if act == ACT_NONE else (F.relu(y) if act == ACT_RELU else F.leaky_relu(y, 0.01))
+    return InstanceNormActFn.apply(x, act, eps)
+
+
+def conv2d_any(m: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """An nn.Conv2d of IGEV's 2-D front on the differentiable HIP route, picked by its geometry:
+      <= 4 input channels, k in {3,5,7}, stride 1 / 2, padding k/2   conv2d_fewin (no input gradient)
+      k in {1,3}, stride 1, padding = dilation (k3) / 0 (k1)          conv2d
+      k3, stride 2, padding 1                                         conv2d_s2
+      k1, stride 2, padding 0                                         conv2d_k1s2
+    Anything else raises."""
+    if not isinstance(m, torch.nn.Conv2d) or isinstance(m, torch.nn.ConvTranspose2d):
+        raise _lib.DiffuVolumeError(f"conv2d_any: an nn.Conv2d, got {type(m).__name__}")
+    k, st, d = m.kernel_size[0], m.stride[0], m.dilation[0]
+    square = m.kernel_size == (k, k) and m.stride == (st, st) and m.dilation == (d, d) and m.groups == 1 and \
+        m.padding_mode == "zeros" and not isinstance(m.padding, str)
+    if square and m.in_channels <= 4 and k in (3, 5, 7) and st in (1, 2) and d == 1 and m.padding == (k // 2, k // 2):
+        return conv2d_fewin(x, m.weight, m.bias, st)
+    if square and st == 1 and k in (1, 3) and m.padding == ((d, d) if k == 3 else (0, 0)):
+        return conv2d(x, m.weight, m.bias, dilation=d)
+    if square and st == 2 and k == 3 and d == 1 and m.padding == (1, 1):
+        return conv2d_s2(x, m.weight, m.bias)
+    if square and st == 2 and k == 1 and m.padding == (0, 0):
+        return conv2d_k1s2(x, m.weight, m.bias)
+    raise _lib.DiffuVolumeError(f"conv2d_any: no training route for {m}")

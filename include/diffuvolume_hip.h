@@ -669,6 +669,31 @@ int dv_gru_gates_bwd_reset_f32(const float* drh, const float* r, const float* h,
 int dv_conv2d_1in_wgrad_f32(const float* x, const float* g, float* dw, int B, int H, int W, int Cout, int k,
                             dv_stream_t stream);
 
+/* ---- training: IGEV's once-per-pair 2-D front (csrc/igev_front_bwd.hip) -------------------------------
+ * What `IGEVStereo_ddim.forward` computes before the cost volume (KITTI15/core/igev_stereo_ddim.py:364-377, :395-398)
+ * needs two backward kernels beside the convolution ones above; both are fp32, contiguous, atomics-free (every output
+ * element written once, the same bits on every launch of a shape).
+ * dv_instance_norm_act_bwd_f32: backward of dv_instance_norm_act_f32 -- nn.InstanceNorm2d (affine=False) + activation of
+ *   BasicConv_IN (core/submodule.py:79-107), the stems (igev_stereo_ddim.py:100-103) and `spx_4` (:104-108) -- over BC
+ *   planes of HW floats.  x: the SAVED PRE-NORM tensor, g: the gradient of the activated output, act in {DV_ACT_NONE,
+ *   DV_ACT_RELU, DV_ACT_LEAKY}.  Mean and rstd are recomputed with the forward's sums (its bits);
+ *     x_hat = (x - mean) * rstd,  gh = g * act'(x_hat)   (act' = 0 / 0.01 where x_hat <= 0, like torch),
+ *     dx = rstd * (gh - mean(gh) - x_hat * mean(gh * x_hat)).
+ *   HW = 1 gives zeros.  dx must not alias x or g.
+ * dv_conv2d_fewin_wgrad_f32: weight gradient of dv_conv2d_fewin_f32 (Cin <= 4, k in {3,5,7}, stride in {1,2}, padding
+ *   k/2) -- `stem_2[0]` (3 -> 32, k3, s2, igev_stereo_ddim.py:100), `cnet.conv1` (3 -> 64, k7, s2, core/extractor.py:197)
+ *   and a plain backbone's `conv_stem` (core/extractor.py:337):
+ *     dw[co,ci,ky,kx] = sum_{b,y,x} g[b,co,y,x] * x[b,ci,y*stride-k/2+ky,x*stride-k/2+kx]   (x zero outside the image)
+ *   x [B,Cin,H,W], g [B,Cout,Ho,Wo] with Ho = (H-1)/stride+1, dw [Cout,Cin,k,k].  The reduction over B*Ho*Wo (bricks of
+ *   8 x 16 output pixels) is split over blocks, every split writes its partial into `workspace`
+ *   (dv_conv2d_fewin_wgrad_workspace_floats floats = splits * Cout * Cin * k * k, at most 48 MB; 0 = unsupported
+ *   arguments) and a second kernel adds the splits in split order.  The images are data: there is no input gradient. */
+int dv_instance_norm_act_bwd_f32(const float* x, const float* g, float* dx, int BC, int HW, float eps, int act,
+                                 dv_stream_t stream);
+size_t dv_conv2d_fewin_wgrad_workspace_floats(int B, int Cin, int H, int W, int Cout, int k, int stride);
+int dv_conv2d_fewin_wgrad_f32(const float* x, const float* g, float* dw, float* workspace, int B, int Cin, int H, int W,
+                              int Cout, int k, int stride, dv_stream_t stream);
+
 /* ---- metrics (SceneFlow/utils/metrics.py:22-65) -------------------------------
  * Per-image sums over pixels with mask!=0: sums[b] = { n_mask, n_gt_pos, sum|gt-est|,
  * n_D1 (err>3 & err/|gt|>0.05), n_err>1, n_err>2, n_err>3, 0 } as fp64 [B,8].
