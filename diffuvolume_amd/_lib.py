@@ -140,11 +140,15 @@ SIGNATURES = {
     "dv_conv2d_wgrad_cat_workspace_floats": (c_size_t, [P, I, I, I, I, I, I]),
     "dv_conv2d_wgrad_cat_f32": (c_int, [P, P, I, P, P, P, I, I, I, I, I, P]),
     "dv_conv2d_1in_wgrad_f32": (c_int, [P, P, P, I, I, I, I, I, P]),
+    "dv_conv2d_wgrad_cat_f16_workspace_floats": (c_size_t, [P, I, I, I, I, I, I]),
+    "dv_conv2d_wgrad_cat_f16": (c_int, [P, P, I, P, P, P, I, I, I, I, I, P]),
     "dv_context_upsample_bwd_f32": (c_int, [P, P, P, P, P, P, I, I, I, c_float, I, P]),
     "dv_deconv2d_k4s2_wgrad_workspace_floats": (c_size_t, [I, I, I, I, I]),
     "dv_deconv2d_k4s2_wgrad_f32": (c_int, [P, P, P, P, I, I, I, I, I, P]),
     "dv_gru_reset_mul_f32": (c_int, [P, P, P, c_size_t, P]),
     "dv_gru_blend_f32": (c_int, [P, P, P, P, c_size_t, P]),
+    "dv_gru_reset_mul_f16": (c_int, [P, P, P, c_size_t, P]),
+    "dv_gru_blend_f16": (c_int, [P, P, P, P, c_size_t, P]),
     "dv_gru_gates_bwd_blend_f32": (c_int, [P, P, P, P, P, P, P, c_size_t, P]),
     "dv_gru_gates_bwd_reset_f32": (c_int, [P, P, P, P, P, c_size_t, P]),
     "dv_instance_norm_act_bwd_f32": (c_int, [P, P, P, I, I, ctypes.c_float, I, P]),

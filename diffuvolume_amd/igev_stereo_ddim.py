@@ -1407,7 +1407,7 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
             self.sqrt_one_minus_alphas_cumprod[t].reshape(-1, 1, 1, 1) * noise
 
     def forward_train(self, image1, image2, flow_full, flow_gt, iters=12, flow_init=None, test_mode=False, *, t=None,
-                      noise=None):
+                      noise=None, amp=False):
         """The reference's train branch (:364-463) -> ``(init_disp [B,1,H,W], disp_preds: iters x [B,1,H,W])``, what
         train_stereo.py:160-163 feeds to ``sequence_loss``; ``disp_up`` of the last iteration under ``test_mode``.  Every
         stage runs on its differentiable HIP route: the 2-D front (``_front2d_train``), the cost volume, the spx heads, the
@@ -1415,14 +1415,35 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
         [B,1,h,w] that is two-hot encoded and diffused (:405-432); ``flow_full`` is unused, as in the reference's train
         branch.  ``t`` ([1], long) / ``noise`` ([B,48,h,w]): the diffusion step and the q_sample noise, by default the
         reference's draws ``torch.randint(0, 1000, (1,))`` and ``randn_like``.  The noisy volume is detached like :436, so
-        `time_embedding` gets no gradient, as in the reference."""
+        `time_embedding` gets no gradient, as in the reference.
+
+        ``amp=True`` is the reference's ``--mixed_precision`` training (train_stereo.py:146-173 with
+        ``autocast(enabled=args.mixed_precision)`` around every update-block call, :444-449): the update block runs at
+        train precision "f16" for this call (``BasicMultiUpdateBlock.set_train_precision``; restored afterwards, also when
+        the call raises) -- the boundary ``mixed_precision=True`` has in inference.  The front, the cost volume, the
+        lookup and the upsampling head stay float32 (a deliberate difference: the reference autocasts them too), and all
+        outputs are float32.  Step through ``torch.amp.GradScaler``: a scaled loss that overflows fp16 inside the block
+        gives Inf / NaN gradients and the scaler skips the step.  The call takes no ``torch.autocast`` of the caller's
+        and ``args.mixed_precision=True`` alone does not select it: both raise and point here."""
         if not self.training:
             raise _lib.DiffuVolumeError("forward_train is the training entry (model.train()); forward is the eval one")
         if not torch.is_grad_enabled():
             raise _lib.DiffuVolumeError("forward_train under no_grad: validation runs model.eval() and forward")
-        if getattr(self.args, "mixed_precision", False) or torch.is_autocast_enabled("cuda"):
-            raise _lib.DiffuVolumeError("IGEVStereo_ddim trains in float32: args.mixed_precision / fp16 / bf16 autocast are "
-                                        "not supported in train mode (mixed-precision training is not implemented)")
+        if torch.is_autocast_enabled("cuda") or (getattr(self.args, "mixed_precision", False) and not amp):
+            raise _lib.DiffuVolumeError("IGEVStereo_ddim.forward_train takes no args.mixed_precision / torch.autocast of "
+                                        "the caller's: mixed-precision training is forward_train(..., amp=True) (the "
+                                        "update block on the fp16 kernels, everything else float32) with "
+                                        "torch.amp.GradScaler")
+        if amp:
+            before = self.update_block.train_precision
+            self.update_block.set_train_precision("f16")
+            try:
+                return self._forward_train(image1, image2, flow_gt, iters, flow_init, test_mode, t, noise)
+            finally:
+                self.update_block.set_train_precision(before)
+        return self._forward_train(image1, image2, flow_gt, iters, flow_init, test_mode, t, noise)
+
+    def _forward_train(self, image1, image2, flow_gt, iters, flow_init, test_mode, t, noise):
         if flow_init is not None:
             raise _lib.DiffuVolumeError("flow_init: the reference's train branch does not read it (:441-457)")
         for name, ten in (("image1", image1), ("image2", image2), ("flow_gt", flow_gt)):
@@ -1430,6 +1451,10 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
                 raise _lib.DiffuVolumeError(f"{name} is on {ten.device}: training runs on the MI355X (no CPU fallback)")
         n_layers = self.args.n_gru_layers
         features_left, stem_2x, match_left, match_right, net_list, inp_list = _front2d_train(self, image1, image2, n_layers)
+        if self.update_block.train_precision == "f16":
+            # as the inference loop under mixed_precision: the reference's front hands the block fp16 tensors (their
+            # gradients pass through the same cast: rounded to fp16, Inf beyond its range -- what GradScaler watches)
+            net_list, inp_list = round_gru_inputs_f16(net_list, inp_list)
         geo, init_disp = self.cost_volume(match_left, match_right, features_left)
         spx_pred = None if test_mode else _spx_init_train(self, features_left[0], stem_2x)
         from .geometry_ddim import Combined_Geo_Encoding_Volume

@@ -20,7 +20,13 @@ single-input-channel ``convd1``).  Their weight gradients run
 on ``dv_conv2d_wgrad_cat_f32`` (csrc/conv2d_wgrad_cat.hip) over the un-materialised concatenation; their input gradients
 are ONE forward launch on the output gradient with the flipped / transposed weights, cut into channel views per
 source; the flipped weights are packed once per plan (the module's ``plans("train")`` slot, dropped with the weight
-key), not per call.
+key), not per call.  Mixed precision (``BasicMultiUpdateBlock.set_train_precision("f16")``, ``forward_train(amp=True)``):
+every plan has an fp16 twin (``f16=True``, the ``plans("train16")`` slot) whose forward and input gradient run on
+``Conv2dF16Plan`` (csrc/conv2d_f16.hip: operands and results rounded to fp16, fp32 accumulation on the fp16 MFMA), whose
+weight gradient runs on ``dv_conv2d_wgrad_cat_f16`` (csrc/conv2d_wgrad_cat_f16.hip, an unrounded float32 dW) and whose gate
+arithmetic rounds like the fp16 epilogues (``dv_gru_reset_mul_f16`` / ``dv_gru_blend_f16``); tensors stay float32 holding
+fp16-exact values, bias gradients stay float32 sums.  ``DV_TRAIN_CONV2D=torch`` at that precision runs the torch
+expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.
 
 IGEV's convex-upsampling head (``igev_stereo_ddim.IGEVUpsampler`` in train mode) uses the third part:
 ``conv_transpose2d_k4`` / ``conv_transpose2d_module``, a ConvTranspose2d(kernel 4, stride 2, padding 1) whose forward is
@@ -43,7 +49,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .submodule import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dPairPlan, Conv2dPlan, Deconv2dK4S2Plan
+from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan,
+                        Deconv2dK4S2Plan)
 from .train3d import _check
 
 
@@ -133,10 +140,13 @@ def conv2d_module(m: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
 
 # ---- IGEV's update block: convolutions over a virtual concatenation, ConvGRU ----------------------------------------
 
-def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int) -> torch.Tensor:
+def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) -> torch.Tensor:
     """dW [Cout, sum(c_i), k, k] of a stride-1, dilation-1 convolution (k 3: padding 1) whose input is the channel
-    concatenation of ``sources`` (1..4 tensors, never materialised) and whose output gradient is ``g``."""
+    concatenation of ``sources`` (1..4 tensors, never materialised) and whose output gradient is ``g``.  ``f16``: on
+    ``dv_conv2d_wgrad_cat_f16`` (both operands rounded to fp16 while staged, fp32 accumulation on the fp16 MFMA, float32
+    result) instead of ``dv_conv2d_wgrad_cat_f32``."""
     import ctypes
+    name = "dv_conv2d_wgrad_cat_f16" if f16 else "dv_conv2d_wgrad_cat_f32"
     sources = [t.contiguous() for t in sources]
     g = g.contiguous()
     b, cout, h, w = g.shape
@@ -147,14 +157,15 @@ def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int) -> torch.Tensor:
     ptrs = (ctypes.c_void_p * len(sources))(*[t.data_ptr() for t in sources])
     chans = (ctypes.c_int * len(sources))(*[t.shape[1] for t in sources])
     lib = _lib.load()
-    n = lib.dv_conv2d_wgrad_cat_workspace_floats(chans, len(sources), b, h, w, cout, k)
+    size = lib.dv_conv2d_wgrad_cat_f16_workspace_floats if f16 else lib.dv_conv2d_wgrad_cat_workspace_floats
+    n = size(chans, len(sources), b, h, w, cout, k)
     if n == 0:
-        raise _lib.DiffuVolumeError(f"dv_conv2d_wgrad_cat_f32 does not take k={k}, channels {list(chans)}, Cout {cout}")
+        raise _lib.DiffuVolumeError(f"{name} does not take k={k}, channels {list(chans)}, Cout {cout}")
     dw = torch.empty((cout, sum(chans), k, k), dtype=torch.float32, device=g.device)
     ws = torch.empty(n, dtype=torch.float32, device=g.device)
     with torch.cuda.device(g.device):
-        _lib.check(lib.dv_conv2d_wgrad_cat_f32(ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h,
-                                               w, cout, k, _lib.stream_ptr()), "dv_conv2d_wgrad_cat_f32")
+        _lib.check(getattr(lib, name)(ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h, w, cout,
+                                      k, _lib.stream_ptr()), name)
     return dw
 
 
@@ -162,16 +173,20 @@ class _InputGradPlan:
     """The input gradient of a stride-1, dilation-1 convolution as a forward launch: the weights flipped and transposed
     ([Cin, Cout, k, k]) and packed ONCE.  ``weights``: one tensor, or several whose outputs are concatenated (ConvGRU's
     z | r pair: the gradient then arrives as one tensor per convolution, read as a virtual concatenation).  A
-    single-channel gradient (DispHead.conv2, 256 -> 1) runs on ``dv_conv2d_1in_f32``."""
+    single-channel gradient (DispHead.conv2, 256 -> 1) runs on ``dv_conv2d_1in_f32``.  ``f16``: the same launch on
+    ``Conv2dF16Plan`` / ``dv_conv2d_1in_f16`` -- gradient and weights rounded to fp16, fp32 accumulation, the input gradient
+    rounded to fp16 as the reference's fp16 input gradients are."""
 
-    def __init__(self, weights):
+    def __init__(self, weights, f16: bool = False):
         w = torch.cat([t.detach() for t in weights], dim=0) if len(weights) > 1 else weights[0].detach()
         self.k = int(w.shape[2])
         wt = (w.transpose(0, 1) if self.k == 1 else w.flip(2, 3).transpose(0, 1)).contiguous()
         self.cin = int(wt.shape[0])
         self.one_in = w.shape[0] == 1 and self.k == 3
         self.wt = wt if self.one_in else None
-        self.plan = None if self.one_in else Conv2dPlan(wt, None, dilation=1, act=ACT_NONE)
+        self.fn1 = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
+        self.plan = None if self.one_in else (Conv2dF16Plan(wt, None, act=ACT_NONE) if f16 else
+                                              Conv2dPlan(wt, None, dilation=1, act=ACT_NONE))
 
     def __call__(self, grads):
         if self.one_in:
@@ -179,8 +194,8 @@ class _InputGradPlan:
             b, _, h, wd = g.shape
             dx = torch.empty((b, self.cin, h, wd), dtype=torch.float32, device=g.device)
             with torch.cuda.device(g.device):
-                _lib.check(_lib.load().dv_conv2d_1in_f32(g.data_ptr(), self.wt.data_ptr(), 0, dx.data_ptr(), b, h, wd,
-                                                         self.cin, 3, ACT_NONE, _lib.stream_ptr()), "dv_conv2d_1in_f32")
+                _lib.check(getattr(_lib.load(), self.fn1)(g.data_ptr(), self.wt.data_ptr(), 0, dx.data_ptr(), b, h, wd,
+                                                          self.cin, 3, ACT_NONE, _lib.stream_ptr()), self.fn1)
             return dx
         return self.plan(list(grads) if len(grads) > 1 else grads[0])
 
@@ -209,17 +224,20 @@ def _act_grad(g: torch.Tensor, out: torch.Tensor, act: int) -> torch.Tensor:
 
 class TrainConvPlan:
     """One nn.Conv2d (3x3 padding 1, or 1x1; stride 1) of the update block for the training route: the forward plan with
-    bias and activation fused, and the packed weights of its input gradient."""
+    bias and activation fused, and the packed weights of its input gradient.  ``f16``: the mixed-precision twin (the
+    module's ``plans("train16")`` slot) -- forward and input gradient on ``Conv2dF16Plan``, the weight gradient on
+    ``dv_conv2d_wgrad_cat_f16``."""
 
-    def __init__(self, conv: torch.nn.Conv2d, act: int):
+    def __init__(self, conv: torch.nn.Conv2d, act: int, f16: bool = False):
         k = conv.kernel_size[0]
         if conv.kernel_size != (k, k) or k not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or \
                 conv.padding != ((k - 1) // 2,) * 2 or conv.groups != 1:
             raise _lib.DiffuVolumeError(f"TrainConvPlan: 3x3 (padding 1) or 1x1, stride 1, dilation 1 only, got {conv}")
         _check(conv.weight, "weight")
-        self.k, self.act, self.cout = k, act, conv.out_channels
-        self.fwd = Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
-        self.bwd = _InputGradPlan([conv.weight])
+        self.k, self.act, self.cout, self.f16 = k, act, conv.out_channels, f16
+        self.fwd = Conv2dF16Plan(conv.weight, conv.bias, act=act) if f16 else \
+            Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
+        self.bwd = _InputGradPlan([conv.weight], f16)
 
 
 class ConvCatFn(torch.autograd.Function):
@@ -244,7 +262,7 @@ class ConvCatFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             # (DispHead.conv2, 256 -> 1, idles 63 of the tile's 64 rows; measured at batch 4, 80x184: 0.205 ms here against
             # 0.261 ms on dv_conv2d_wgrad_f32, so it stays on this kernel: a 1 x 2304 reduction is not worth a route)
-            dw = conv2d_cat_weight_grad(sources, gp, plan.k)
+            dw = conv2d_cat_weight_grad(sources, gp, plan.k, plan.f16)
         if ctx.needs_input_grad[2]:
             db = gp.sum(dim=(0, 2, 3))
         dsrc = [None] * len(sources)
@@ -258,10 +276,12 @@ class Conv1InFn(torch.autograd.Function):
     """relu(conv(x) + bias) of a single-input-channel k x k convolution (BasicMotionEncoder.convd1, 7x7): forward on
     ``dv_conv2d_1in_f32`` (the inference kernel), weight gradient on ``dv_conv2d_1in_wgrad_f32`` (fixed summation order:
     MIOpen's backward-weights of this shape does not return the same bits twice).  The input gradient -- the reference
-    always detaches ``disp`` -- is a 64 -> 1 convolution left to PyTorch."""
+    always detaches ``disp`` -- is a 64 -> 1 convolution left to PyTorch.  ``f16``: the forward on ``dv_conv2d_1in_f16``;
+    the weight gradient stays on the float32 kernel, fed the fp16-rounded ``disp`` (one channel by 49 taps is not an MFMA
+    shape)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, f16=False):
         _check(x, "disp")
         _check(weight, "weight")
         x, wt = x.contiguous(), weight.detach().contiguous()
@@ -270,10 +290,11 @@ class Conv1InFn(torch.autograd.Function):
         if cin != 1 or wt.shape[1] != 1 or k != 7:
             raise _lib.DiffuVolumeError(f"Conv1InFn: one input channel, k = 7, got {tuple(wt.shape)}")
         out = torch.empty((b, wt.shape[0], h, w), dtype=torch.float32, device=x.device)
+        fn = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dv_conv2d_1in_f32(x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
-                                                     out.shape[1], k, ACT_RELU, _lib.stream_ptr()), "dv_conv2d_1in_f32")
-        ctx.save_for_backward(x, weight, out)
+            _lib.check(getattr(_lib.load(), fn)(x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
+                                                out.shape[1], k, ACT_RELU, _lib.stream_ptr()), fn)
+        ctx.save_for_backward(x.half().float() if f16 else x, weight, out)
         return out
 
     @staticmethod
@@ -292,26 +313,35 @@ class Conv1InFn(torch.autograd.Function):
             db = gp.sum(dim=(0, 2, 3))
         if ctx.needs_input_grad[0]:
             dx = F.conv2d(gp, weight.detach().flip(2, 3).transpose(0, 1), None, padding=k // 2)
-        return dx, dw, db
+        return dx, dw, db, None
 
 
-def conv_1in_relu(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+def _autocast16(fn):
+    """The torch route at "f16" precision: the expression under a real fp16 autocast, the result as float32."""
+    with torch.autocast("cuda", dtype=torch.float16):
+        return fn().float()
+
+
+def conv_1in_relu(conv: torch.nn.Conv2d, x: torch.Tensor, f16: bool = False) -> torch.Tensor:
     """relu(conv(x)) for a single-input-channel layer on the training route."""
     if route() == "torch":
-        return F.relu(conv(x))
-    return Conv1InFn.apply(x, conv.weight, conv.bias)
+        return _autocast16(lambda: F.relu(conv(x))) if f16 else F.relu(conv(x))
+    return Conv1InFn.apply(x, conv.weight, conv.bias, f16)
 
 
-def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources) -> torch.Tensor:
+def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources, f16: bool = False) -> torch.Tensor:
     """act(conv(cat(sources))) for the training route of the update block.  ``plan``: a callable that returns the
-    layer's TrainConvPlan; it is only called (and the plan only built) on the HIP route."""
+    layer's TrainConvPlan; it is only called (and the plan only built) on the HIP route.  ``f16``: the module's train
+    precision is "f16" (the plan is then its fp16 twin; the torch route runs under a real fp16 autocast)."""
     sources = list(sources) if isinstance(sources, (list, tuple)) else [sources]
     if route() == "torch":
-        x = torch.cat(sources, dim=1) if len(sources) > 1 else sources[0]
-        y = F.conv2d(x, conv.weight, conv.bias, padding=(conv.kernel_size[0] - 1) // 2)
-        return {ACT_NONE: lambda t: t, ACT_RELU: F.relu, ACT_SIGMOID: torch.sigmoid, ACT_TANH: torch.tanh}[act](y)
+        def expr():
+            x = torch.cat(sources, dim=1) if len(sources) > 1 else sources[0]
+            y = F.conv2d(x, conv.weight, conv.bias, padding=(conv.kernel_size[0] - 1) // 2)
+            return {ACT_NONE: lambda t: t, ACT_RELU: F.relu, ACT_SIGMOID: torch.sigmoid, ACT_TANH: torch.tanh}[act](y)
+        return _autocast16(expr) if f16 else expr()
     p = plan()
-    assert p.act == act
+    assert p.act == act and p.f16 == f16
     return ConvCatFn.apply(p, conv.weight, conv.bias, *sources)
 
 
@@ -323,21 +353,31 @@ def _gates(fn: str, *args) -> None:
 
 class GRUTrainPlan:
     """A ConvGRU for the training route: the z | r pair launch (sigmoid fused, no ``mul``), the candidate's plan (tanh
-    fused, no blend) and the packed weights of the two input gradients."""
+    fused, no blend) and the packed weights of the two input gradients.  ``f16``: the mixed-precision twin on
+    ``Conv2dF16Plan`` (the z | r pair without ``mul``, the candidate without ``blend``)."""
 
-    def __init__(self, gru):
+    def __init__(self, gru, f16: bool = False):
         for c in (gru.convz, gru.convr, gru.convq):
             _check(c.weight, "weight")
-        self.hidden = gru.convz.out_channels
-        self.zr = Conv2dPairPlan((gru.convz.weight, gru.convz.bias), (gru.convr.weight, gru.convr.bias), ACT_SIGMOID)
-        self.q = Conv2dPlan(gru.convq.weight, None, dilation=1, act=ACT_TANH, bias=gru.convq.bias)
-        self.zr_bwd = _InputGradPlan([gru.convz.weight, gru.convr.weight])
-        self.q_bwd = _InputGradPlan([gru.convq.weight])
+        self.hidden, self.f16 = gru.convz.out_channels, f16
+        if f16:
+            self.zr = Conv2dF16Plan(gru.convz.weight, gru.convz.bias, ACT_SIGMOID, pair=(gru.convr.weight, gru.convr.bias))
+            self.q = Conv2dF16Plan(gru.convq.weight, gru.convq.bias, ACT_TANH)
+        else:
+            self.zr = Conv2dPairPlan((gru.convz.weight, gru.convz.bias), (gru.convr.weight, gru.convr.bias), ACT_SIGMOID)
+            self.q = Conv2dPlan(gru.convq.weight, None, dilation=1, act=ACT_TANH, bias=gru.convq.bias)
+        self.zr_bwd = _InputGradPlan([gru.convz.weight, gru.convr.weight], f16)
+        self.q_bwd = _InputGradPlan([gru.convq.weight], f16)
+        self.mul, self.blend = ("dv_gru_reset_mul_f16", "dv_gru_blend_f16") if f16 else \
+            ("dv_gru_reset_mul_f32", "dv_gru_blend_f32")
 
 
 class ConvGRUFn(torch.autograd.Function):
     """One ConvGRU call (update.py:33-40).  Saved for the backward: h, the x sources, z, r, q -- no concatenation, no
-    r*h, no 1-z or z*q.  Inputs: plan, six parameters, h, cz, cr, cq, then the x sources."""
+    r*h, no 1-z or z*q.  Inputs: plan, six parameters, h, cz, cr, cq, then the x sources.  The precision is the plan's:
+    with an fp16 plan the gate kernels round like conv2d_f16.hip's epilogues (the eval forward's bits under fp16
+    autocast), the gate backward stays float32 arithmetic on the fp16-exact saved values (the convolutions that consume
+    its outputs round their operands anyway) and the weight gradients run on ``dv_conv2d_wgrad_cat_f16``."""
 
     @staticmethod
     def forward(ctx, plan, wz, bz, wr, br, wq, bq, h, cz, cr, cq, *xs):
@@ -345,12 +385,12 @@ class ConvGRUFn(torch.autograd.Function):
             _check(t, "ConvGRU input")
         h, cz, cr, cq = (t.contiguous() for t in (h, cz, cr, cq))
         xs = [t.contiguous() for t in xs]
-        z, r = plan.zr([h, *xs], residual=(cz, cr))
+        z, r = plan.zr([h, *xs], residual=(cz, cr), mul=(None, None))
         rh = torch.empty_like(h)
-        _gates("dv_gru_reset_mul_f32", r, h, rh, h.numel())
+        _gates(plan.mul, r, h, rh, h.numel())
         q = plan.q([rh, *xs], residual=cq)
         out = torch.empty_like(h)
-        _gates("dv_gru_blend_f32", z, q, h, out, h.numel())
+        _gates(plan.blend, z, q, h, out, h.numel())
         ctx.plan = plan
         ctx.save_for_backward(h, z, r, q, *xs)
         return out
@@ -365,16 +405,16 @@ class ConvGRUFn(torch.autograd.Function):
         dq, dz, dh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
         _gates("dv_gru_gates_bwd_blend_f32", g, z, q, h, dq, dz, dh, n)
         rh = torch.empty_like(h)
-        _gates("dv_gru_reset_mul_f32", r, h, rh, n)                   # (recomputed: the forward's bits)
+        _gates(plan.mul, r, h, rh, n)                                 # (recomputed: the forward's bits)
         dq_in = plan.q_bwd([dq])                                      # d[rh | x...]
         dr = torch.empty_like(h)
         _gates("dv_gru_gates_bwd_reset_f32", dq_in[:, :plan.hidden].contiguous(), r, h, dr, dh, n)
         dzr_in = plan.zr_bwd([dz, dr])                                # d[h | x...]
         dh += dzr_in[:, :plan.hidden]
         hx = [h, *xs]
-        dwz = conv2d_cat_weight_grad(hx, dz, 3) if need[1] else None
-        dwr = conv2d_cat_weight_grad(hx, dr, 3) if need[3] else None
-        dwq = conv2d_cat_weight_grad([rh, *xs], dq, 3) if need[5] else None
+        dwz = conv2d_cat_weight_grad(hx, dz, 3, plan.f16) if need[1] else None
+        dwr = conv2d_cat_weight_grad(hx, dr, 3, plan.f16) if need[3] else None
+        dwq = conv2d_cat_weight_grad([rh, *xs], dq, 3, plan.f16) if need[5] else None
         dbz = dz.sum(dim=(0, 2, 3)) if need[2] else None
         dbr = dr.sum(dim=(0, 2, 3)) if need[4] else None
         dbq = dq.sum(dim=(0, 2, 3)) if need[6] else None
@@ -387,20 +427,26 @@ class ConvGRUFn(torch.autograd.Function):
                 dr if need[9] else None, dq if need[10] else None, *dxs)
 
 
-def conv_gru(plan, gru, h, cz, cr, cq, *xs) -> torch.Tensor:
-    """ConvGRU.forward for the training route (the reference's expression under DV_TRAIN_CONV2D=torch).  ``plan``: a
-    callable that returns the GRUTrainPlan, only called on the HIP route."""
+def conv_gru(plan, gru, h, cz, cr, cq, *xs, f16: bool = False) -> torch.Tensor:
+    """ConvGRU.forward for the training route (the reference's expression under DV_TRAIN_CONV2D=torch; at "f16"
+    precision that expression under a real fp16 autocast, on fp16 tensors like the reference's).  ``plan``: a callable
+    that returns the GRUTrainPlan, only called on the HIP route."""
     if route() == "torch":
-        x = torch.cat(xs, dim=1)
-        hx = torch.cat([h, x], dim=1)
-        z = torch.sigmoid(gru.convz(hx) + cz)
-        r = torch.sigmoid(gru.convr(hx) + cr)
-        q = torch.tanh(gru.convq(torch.cat([r * h, x], dim=1)) + cq)
-        return (1 - z) * h + z * q
+        def expr():
+            hh, zz, rr, qq = (t.half() for t in (h, cz, cr, cq)) if f16 else (h, cz, cr, cq)
+            x = torch.cat([t.half() for t in xs] if f16 else xs, dim=1)
+            hx = torch.cat([hh, x], dim=1)
+            z = torch.sigmoid(gru.convz(hx) + zz)
+            r = torch.sigmoid(gru.convr(hx) + rr)
+            q = torch.tanh(gru.convq(torch.cat([r * hh, x], dim=1)) + qq)
+            return (1 - z) * hh + z * q
+        return _autocast16(expr) if f16 else expr()
     if len(xs) > 3:                                     # the kernels take four sources: [h | x1 | x2 | x3]
         xs = (torch.cat(xs[:-2], dim=1),) + tuple(xs[-2:])
     c = gru.convz, gru.convr, gru.convq
-    return ConvGRUFn.apply(plan(), c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias, h, cz, cr, cq, *xs)
+    p = plan()
+    assert p.f16 == f16
+    return ConvGRUFn.apply(p, c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias, h, cz, cr, cq, *xs)
 
 
 # ---- IGEV's convex-upsampling head: ConvTranspose2d(kernel 4, stride 2, padding 1) -----------------------------------

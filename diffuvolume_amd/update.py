@@ -22,9 +22,19 @@ arithmetic and its backward on csrc/conv2d_wgrad_cat.hip's elementwise kernels),
 ``dv_conv2d_wgrad_cat_f32`` over the virtual concatenations, input gradients on the forward kernels with flipped weights
 packed once per weight key (the ``plans("train")`` slot).  ``convd1`` (7x7, one input channel) runs through autograd
 there (``train2d.Conv1InFn``) so that it learns although ``disp`` is detached; ``pool2x`` / ``interp`` keep their
-autograd dispatch.  fp32 only:
-fp16 autocast raises.  ``DV_TRAIN_CONV2D=torch`` sends the convolutions and the gate arithmetic to torch expressions.
+autograd dispatch.  ``DV_TRAIN_CONV2D=torch`` sends the convolutions and the gate arithmetic to torch expressions.
 Train mode under ``torch.no_grad()`` runs the inference kernels.
+
+Train precision: float32 by default, and then fp16 / bf16 autocast raises in train mode.
+``BasicMultiUpdateBlock.set_train_precision("f16")`` (what ``IGEVStereo_ddim.forward_train(amp=True)`` sets for the call)
+is the reference's ``--mixed_precision`` training (train_stereo.py:146-173): the block and its five child modules take
+their ``plans("train16")`` slot -- forward and input gradients on the fp16 plans above with the reference's rounding
+points (the training forward has the bits of the eval forward under fp16 autocast), weight gradients on
+``dv_conv2d_wgrad_cat_f16`` (fp16 operands, fp32 accumulation; dW is kept as the unrounded float32 sum where the
+reference rounds it to fp16), the gate backward in float32 on the fp16-exact saved values.  The kernels do the rounding,
+so the precision holds with or without a caller's fp16 autocast; fp16 inputs are converted to float32 once on entry,
+all outputs and gradients are float32, bf16 autocast is refused.  Under ``DV_TRAIN_CONV2D=torch`` that precision runs the
+torch expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.
 """
 from __future__ import annotations
 
@@ -51,12 +61,30 @@ def autocast_f16() -> bool:
 class _Planned(PlanCache, nn.Module):
     """Two plan slots (submodule.PlanCache): the fp32 plans (``plans()``) and the fp16-autocast ones (``plans("f16")``),
     each built lazily by the module's ``_build`` / ``_build16``, and the training route's (``plans("train")``,
-    ``_build_train``: forward plans plus the packed weights of the input gradients)."""
+    ``_build_train``: forward plans plus the packed weights of the input gradients; ``plans("train16")``: their fp16
+    twins, taken when the module's train precision is "f16")."""
+
+    _train_precision = "f32"
 
     def _build_plans(self, slot):
-        if slot == "train":
-            return self._build_train()
+        if slot in ("train", "train16"):
+            return self._build_train(slot == "train16")
         return self._build16() if slot == "f16" else self._build()
+
+    def set_train_precision(self, precision: str):
+        """"f32" (default: train mode refuses autocast) or "f16" (mixed-precision training on the fp16 kernels, with or
+        without a caller's fp16 autocast) for this module and every module of the block below it -- each is a training
+        entry of its own."""
+        if precision not in ("f32", "f16"):
+            raise ValueError(f"train precision must be 'f32' or 'f16', got {precision!r}")
+        for m in self.modules():
+            if isinstance(m, _Planned):
+                m._train_precision = precision
+        return self
+
+    @property
+    def train_precision(self) -> str:
+        return self._train_precision
 
 
 def _plan(conv: nn.Conv2d, act: int) -> Conv2dPlan:
@@ -86,16 +114,16 @@ class DispHead(_Planned):
     def _build16(self):
         return _plan16(self.conv1, ACT_RELU), _plan16(self.conv2, ACT_NONE)
 
-    def _build_train(self):
+    def _build_train(self, f16=False):
         from .train2d import TrainConvPlan
-        return TrainConvPlan(self.conv1, ACT_RELU), TrainConvPlan(self.conv2, ACT_NONE)
+        return TrainConvPlan(self.conv1, ACT_RELU, f16), TrainConvPlan(self.conv2, ACT_NONE, f16)
 
     def forward(self, x):
         if _training(self):
             from .train2d import conv_cat
-            _train_entry(self)
-            return conv_cat(lambda: self.plans("train")[1], self.conv2, ACT_NONE,
-                            conv_cat(lambda: self.plans("train")[0], self.conv1, ACT_RELU, x))
+            f16, slot = _train_entry(self)
+            return conv_cat(lambda: self.plans(slot)[1], self.conv2, ACT_NONE,
+                            conv_cat(lambda: self.plans(slot)[0], self.conv1, ACT_RELU, _f32(x) if f16 else x, f16), f16)
         c1, c2 = self.plans("f16") if autocast_f16() else self.plans()
         return c2(c1(_f32(x)))
 
@@ -121,15 +149,18 @@ class ConvGRU(_Planned):
         return (Conv2dF16Plan(self.convz.weight, self.convz.bias, ACT_SIGMOID, pair=(self.convr.weight, self.convr.bias)),
                 _plan16(self.convq, ACT_TANH))
 
-    def _build_train(self):
+    def _build_train(self, f16=False):
         from .train2d import GRUTrainPlan
-        return GRUTrainPlan(self)
+        return GRUTrainPlan(self, f16)
 
     def forward(self, h, cz, cr, cq, *x_list):
         if _training(self):
             from .train2d import conv_gru
-            _train_entry(self)
-            return conv_gru(lambda: self.plans("train"), self, h, cz, cr, cq, *x_list)
+            f16, slot = _train_entry(self)
+            if f16:
+                h, cz, cr, cq = _f32(h), _f32(cz), _f32(cr), _f32(cq)
+                x_list = tuple(_f32(t) for t in x_list)
+            return conv_gru(lambda: self.plans(slot), self, h, cz, cr, cq, *x_list, f16=f16)
         if autocast_f16():
             # (the fp16 plans round z, r*h and the blend (1-z)*h + z*q at the reference's points; see csrc/conv2d_f16.hip)
             pzr, pq = self.plans("f16")
@@ -183,9 +214,9 @@ class BasicMotionEncoder(_Planned):
                                   torch.cat([b, b.new_zeros(1)]), act=ACT_RELU)
         return p
 
-    def _build_train(self):
+    def _build_train(self, f16=False):
         from .train2d import TrainConvPlan
-        return {n: TrainConvPlan(getattr(self, n), ACT_RELU) for n in ("convc1", "convc2", "convd2", "conv")}
+        return {n: TrainConvPlan(getattr(self, n), ACT_RELU, f16) for n in ("convc1", "convc2", "convd2", "conv")}
 
     def forward(self, disp, corr):
         return self.features(disp, corr)                # update.py:94 (the reference's return value)
@@ -197,14 +228,16 @@ class BasicMotionEncoder(_Planned):
         bias learn although `disp` is detached."""
         from .geometry_ddim import GeoLookupRequest
         from .train2d import conv_1in_relu, conv_cat
-        _train_entry(self)
-        p = lambda n: (lambda: self.plans("train")[n])
+        f16, slot = _train_entry(self)
+        p = lambda n: (lambda: self.plans(slot)[n])
         if isinstance(corr, GeoLookupRequest):
             corr = corr.materialize()              # the fused lookup + 1x1 is inference-only
-        cor = conv_cat(p("convc2"), self.convc2, ACT_RELU, conv_cat(p("convc1"), self.convc1, ACT_RELU, corr))
-        disp_ = conv_cat(p("convd2"), self.convd2, ACT_RELU, conv_1in_relu(self.convd1, disp))
-        out = conv_cat(p("conv"), self.conv, ACT_RELU, [cor, disp_])
-        return torch.cat([out, disp], dim=1)
+        if f16:
+            disp, corr = _f32(disp), _f32(corr)
+        cor = conv_cat(p("convc2"), self.convc2, ACT_RELU, conv_cat(p("convc1"), self.convc1, ACT_RELU, corr, f16), f16)
+        disp_ = conv_cat(p("convd2"), self.convd2, ACT_RELU, conv_1in_relu(self.convd1, disp, f16), f16)
+        out = conv_cat(p("conv"), self.conv, ACT_RELU, [cor, disp_], f16)
+        return torch.cat([out, disp], dim=1)       # (channel 127: the float32 disp, unrounded, as under autocast)
 
     def features(self, disp, corr):
         """The motion features [B,128,h,w] = [conv output (127) | disp (1)], update.py:88-94."""
@@ -264,15 +297,23 @@ def _training(m) -> bool:
 
 def _train_entry(m):
     """Every module of the block is a training entry of its own (ConvGRU, DispHead, BasicMotionEncoder called directly):
-    fp32 only, and the packed weights follow the weight key, so an optimizer step since the last call drops them here."""
-    _no_autocast()
+    its train precision decides the route -- "f32" refuses autocast, "f16" takes the fp16 plans with or without the
+    caller's fp16 autocast (bf16 raises) -- and the packed weights follow the weight key, so an optimizer step since the
+    last call drops them here.  Returns (f16, the plan slot)."""
+    f16 = m._train_precision == "f16"
+    if f16:
+        autocast_f16()                      # (raises on bf16)
+    else:
+        _no_autocast()
     m.refresh_plans()
+    return f16, ("train16" if f16 else "train")
 
 
 def _no_autocast():
     if torch.is_autocast_enabled("cuda"):
-        raise _lib.DiffuVolumeError("the update block trains in float32: fp16 / bf16 autocast is not supported in train "
-                                    "mode (mixed-precision training is not implemented)")
+        raise _lib.DiffuVolumeError("the update block trains in float32 at its default train precision: fp16 / bf16 "
+                                    "autocast is not supported in train mode (mixed-precision training: "
+                                    "set_train_precision('f16'), or IGEVStereo_ddim.forward_train(amp=True))")
 
 
 def _hip_ok(x, what):
@@ -340,15 +381,20 @@ class BasicMultiUpdateBlock(_Planned):
     def _build16(self):
         return _plan16(self.mask_feat_4[0], ACT_RELU)
 
-    def _build_train(self):
+    def _build_train(self, f16=False):
         from .train2d import TrainConvPlan
-        return TrainConvPlan(self.mask_feat_4[0], ACT_RELU)
+        return TrainConvPlan(self.mask_feat_4[0], ACT_RELU, f16)
 
     def _forward_train(self, net, inp, corr, disp, iter04, iter08, iter16, update, mask):
         """The reference's forward (update.py:121-142) on the differentiable route, one stream.  The plans of the whole
         block follow the weight key: an optimizer step between two calls drops them here."""
         from .train2d import _check, conv_cat
-        _train_entry(self)
+        f16, slot = _train_entry(self)
+        if f16:                   # an autocast caller's fp16 tensors: float32 once, here (the list objects are kept)
+            for i in range(len(net)):
+                net[i] = _f32(net[i])
+            inp = [[_f32(t) for t in level] for level in inp]
+            corr, disp = _f32(corr), _f32(disp)
         for t in (*net, *(t for level in inp for t in level), disp):
             if isinstance(t, torch.Tensor):
                 _check(t, "update block input")
@@ -370,7 +416,7 @@ class BasicMultiUpdateBlock(_Planned):
         if not update:
             return net
         delta_disp = self.disp_head(net[0])
-        mask_feat_4 = conv_cat(lambda: self.plans("train"), self.mask_feat_4[0], ACT_RELU, net[0]) if mask else None
+        mask_feat_4 = conv_cat(lambda: self.plans(slot), self.mask_feat_4[0], ACT_RELU, net[0], f16) if mask else None
         return net, mask_feat_4, delta_disp
 
     import os as _os

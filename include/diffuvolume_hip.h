@@ -669,6 +669,28 @@ int dv_gru_gates_bwd_reset_f32(const float* drh, const float* r, const float* h,
 int dv_conv2d_1in_wgrad_f32(const float* x, const float* g, float* dw, int B, int H, int W, int Cout, int k,
                             dv_stream_t stream);
 
+/* ---- mixed-precision training of the update block (csrc/conv2d_wgrad_cat_f16.hip) ----------------------
+ * dv_conv2d_wgrad_cat_f16: the weight gradient of dv_conv2d_wgrad_cat_f32 (same arguments, same virtual concatenation)
+ * as KITTI15/core/update.py:26-142 computes it under `autocast(enabled=args.mixed_precision)` (train_stereo.py:146-173):
+ *   dw[co, ci, ky, kx] = sum_{b, y, x} r16(g[b, co, y, x]) * r16(X[b, ci, y + ky - p, x + kx - p])
+ * both float32 operands rounded to fp16 (nearest even) while they are staged, products accumulated in fp32 on
+ * v_mfma_f32_16x16x32_f16, dw written as UNROUNDED float32 (the reference rounds it to fp16 before the cast back to the
+ * float32 parameter: a deliberate difference).  A g or x beyond the fp16 range becomes Inf, and Inf / NaN appears in dw.
+ * 64 x 64 block tiles, bricks of 4 x 32 output positions, K split over blocks into `workspace`
+ * (dv_conv2d_wgrad_cat_f16_workspace_floats floats, at most 48 MB; 0 = unsupported arguments), summed in split order by a
+ * second kernel: no atomics, the same bits on every launch of a shape. */
+size_t dv_conv2d_wgrad_cat_f16_workspace_floats(const int* channels, int n_inputs, int B, int H, int W, int Cout, int k);
+int dv_conv2d_wgrad_cat_f16(const float* const* inputs, const int* channels, int n_inputs, const float* g, float* dw,
+                            float* workspace, int B, int H, int W, int Cout, int k, dv_stream_t stream);
+
+/* ConvGRU gate arithmetic of the training forward with the rounding points of dv_conv2d_f16_cat's epilogues (every
+ * result rounded to fp16, the operands taken as they are: fp16-exact on the route):
+ *   dv_gru_reset_mul_f16   rh = r16(r * h)
+ *   dv_gru_blend_f16       out = r16(r16(r16(1 - z) * h) + r16(z * q))
+ * The backward of both stays on dv_gru_gates_bwd_*_f32. */
+int dv_gru_reset_mul_f16(const float* r, const float* h, float* rh, size_t n, dv_stream_t stream);
+int dv_gru_blend_f16(const float* z, const float* q, const float* h, float* out, size_t n, dv_stream_t stream);
+
 /* ---- training: IGEV's once-per-pair 2-D front (csrc/igev_front_bwd.hip) -------------------------------
  * What `IGEVStereo_ddim.forward` computes before the cost volume (KITTI15/core/igev_stereo_ddim.py:364-377, :395-398)
  * needs two backward kernels beside the convolution ones above; both are fp32, contiguous, atomics-free (every output
