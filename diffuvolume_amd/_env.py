@@ -30,7 +30,7 @@ KNOBS = {
                         "gather) instead of the HIP forward kernels and their HIP backward kernels (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
-    "DV_IGEV_GRAPH": ("0", "igev_stereo_ddim.IGEVDiffusionLoop.use_graph at import",
+    "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",
                       "1 = replay the GRU iterations of a DDIM step as a hipGraph (same bits, no gain measured)"),
     "DV_DIST_BACKEND": ("nccl on GPUs, gloo on CPUs", "distributed.init_from_env()", "torch.distributed backend of the metric reduce"),
     "DV_BENCH_OVERSUBSCRIBE": ("unset", "bench.py", "1 = let N ranks share fewer GPUs (plumbing test of the N-rank path only)"),

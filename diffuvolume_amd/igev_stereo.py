@@ -36,7 +36,7 @@ class IGEVStereo(IGEVStereo_ddim):
         with torch.no_grad():
             features_left, stem_2x, init_disp, net_list, inp_list, geo_fn = self._front(image1, image2)
             spx_pred = None
-            if not test_mode:                            # :187-191 (2-D InstanceNorm heads, once per pair: PyTorch)
+            if not test_mode:                            # :187-191 (2-D InstanceNorm heads, once per pair)
                 spx_pred = F.softmax(hip_sequential(self.spx, self.spx_2(hip_sequential(self.spx_4, features_left[0]), stem_2x)), 1)
             b, _, h, w = init_disp.shape
             coords = torch.arange(w, dtype=torch.float32, device=init_disp.device).view(1, 1, 1, w).expand(b, 1, h, w).contiguous()

@@ -28,13 +28,13 @@ arithmetic rounds like the fp16 epilogues (``dv_gru_reset_mul_f16`` / ``dv_gru_b
 fp16-exact values, bias gradients stay float32 sums.  ``DV_TRAIN_CONV2D=torch`` at that precision runs the torch
 expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.
 
-IGEV's convex-upsampling head (``igev_stereo_ddim.IGEVUpsampler`` in train mode) uses the third part:
+IGEV's convex-upsampling head (``igev_upsample.IGEVUpsampler`` in train mode) uses the third part:
 ``conv_transpose2d_k4`` / ``conv_transpose2d_module``, a ConvTranspose2d(kernel 4, stride 2, padding 1) whose forward is
 ``Deconv2dK4S2Plan``'s (four parity 3x3 convolutions + pixel shuffle), whose input gradient is ONE 3x3 forward launch on
 the pixel-unshuffled output gradient with the flipped parity weights (``TrainDeconvPlan``, packed once per plan) and
 whose weight gradient is ``dv_deconv2d_k4s2_wgrad_f32`` (csrc/deconv2d_k4_bwd.hip).
 
-IGEV's once-per-pair 2-D front (``igev_stereo_ddim.IGEVFront2d`` / ``IGEVStereo_ddim.forward_train``) uses the fourth
+IGEV's once-per-pair 2-D front (``igev_front2d.IGEVFront2d`` / ``IGEVStereo_ddim.forward_train``) uses the fourth
 part: ``conv2d_s2`` (3x3, stride 2: forward on ``Conv2dPlan(stride=2)``, both gradients on the k4 transposed-convolution
 kernels above through an exact identity), ``conv2d_k1s2`` (the 1x1 stride-2 ``downsample``), ``conv2d_fewin`` (the image
 convolutions: weight gradient on ``dv_conv2d_fewin_wgrad_f32``, no input gradient), ``instance_norm_act`` (backward on
