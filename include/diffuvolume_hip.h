@@ -10,6 +10,11 @@
  *    the reference's own layout (NCHW / NCDHW); outputs are caller-allocated;
  *  - nothing here allocates, frees, synchronises or keeps global mutable state;
  *    calls are re-entrant and are enqueued on `stream` of the current device;
+ *  - alignment: a tensor operand needs only the alignment of its element type (4 bytes for float, 8 for double) unless
+ *    the entry says otherwise below.  16-byte aligned operands on rows of whole quads (W or H*W a multiple of 4) select
+ *    the vector loads / stores; any other placement takes the element-wise bodies and gives the same values to within
+ *    the entry's rounding.  Packed weights (`wpacked`, whatever packer made them) must be 16-byte aligned: the entries
+ *    that check it return DV_ERR_ALIGN.  A refused call launches nothing and writes nothing;
  *  - return value: 0 = ok, <0 = DV_ERR_* (bad argument), >0 = hipError_t.
  */
 #ifndef DIFFUVOLUME_HIP_H
@@ -149,7 +154,8 @@ int dv_conv3d_wino_f32(const float* in, const float* wpacked, const float* ch_sc
  * LDS after the channel loop).  fp32 operands and accumulation on v_mfma_f32_16x16x4_f32; the transforms only add /
  * subtract, measured error no larger than the in-plane form's (tools/probes/wino_f222_numerics.py).  No filter prologue
  * (a call with `in_scale` takes dv_conv3d_wino_f32).  dv_conv3d_wino3_supported: 1 when four channel volumes of the
- * input fit 31-bit byte offsets. */
+ * input fit 31-bit byte offsets.  `in` must be 16-byte aligned (its rows are staged as quads): DV_ERR_ALIGN otherwise;
+ * `out` / `residual` may have any float alignment. */
 size_t dv_conv3d_wino3_packed_floats(int Cin, int Cout);
 int dv_conv3d_wino3_supported(int Cin, int Cout, int D, int H, int W);
 int dv_conv3d_wino3_pack_weights_f32(const float* w /*[Cout,Cin,3,3,3]*/, float* wpacked, int Cin, int Cout,
@@ -165,8 +171,9 @@ int dv_conv3d_wino3_f32(const float* in, const float* wpacked, const float* ch_s
  * by the pack), so results differ from dv_conv3d_f32(stride = 2) by fp32 rounding of one extra subtraction per operand.
  *   y = act( conv_s2(in) * ch_scale[co] + ch_bias[co] + residual )
  * 64 output channels per block and rows that travel as 16-byte quads: dv_conv3d_s2pp_supported says whether a layer
- * qualifies (Cout a multiple of 64, W a multiple of 4, D*H*W*4 <= 2^30; `in` 16-byte aligned), dv_conv3d_s2pp_f32 returns
- * DV_ERR_UNSUPPORTED otherwise.  Persistent launch: one persistent block per CU, two tiles at a time.
+ * qualifies (Cout a multiple of 64, W a multiple of 4, D*H*W*4 <= 2^30), dv_conv3d_s2pp_f32 returns DV_ERR_UNSUPPORTED
+ * otherwise.  `in` must be 16-byte aligned: DV_ERR_ALIGN otherwise; `out` / `residual` may have any float alignment.
+ * Persistent launch: one persistent block per CU, two tiles at a time.
  * `wpacked` from dv_conv3d_s2pp_pack_weights_f32. */
 int dv_conv3d_s2pp_supported(int Cin, int Cout, int D, int H, int W);
 size_t dv_conv3d_s2pp_packed_floats(int Cin, int Cout);
@@ -274,7 +281,8 @@ int dv_conv2d_wino_cat_f32(const float* const* inputs, const int* channels, int 
 /* Two 3x3 convolutions of the SAME input in one launch: ConvGRU's z and r gates (KITTI15/core/update.py:33-35,
  * `convz(hx)` and `convr(hx)`).  `wpacked` / `ch_scale` / `ch_bias` hold the Cout1 + Cout2 output channels back to back
  * (pack the concatenated weight; Cout1 % 32 == 0); channels < Cout1 go to out1 [B,Cout1,H,W] with residual1 / mul1,
- * the others to out2 [B,Cout2,H,W] with residual2 / mul2:  out_g = act(conv_g * scale + bias + residual_g) * mul_g. */
+ * the others to out2 [B,Cout2,H,W] with residual2 / mul2:  out_g = act(conv_g * scale + bias + residual_g) * mul_g.
+ * out2 / residual2 / mul2 must be 16-byte aligned (DV_ERR_ALIGN otherwise); out1 / residual1 / mul1 need not be. */
 int dv_conv2d_wino_cat_pair_f32(const float* const* inputs, const int* channels, int n_inputs, const float* wpacked,
                                 const float* ch_scale, const float* ch_bias, const float* residual1, const float* mul1,
                                 float* out1, const float* residual2, const float* mul2, float* out2, int B, int H,
@@ -314,7 +322,7 @@ int dv_conv2d_wino_cat_pair_ksplit_f32(const float* const* inputs, const int* ch
 
 /* Space-to-batch for the dilated layers of refinenet_version3 (KITTI12/models/pwcnet_ddim.py:251-306), csrc/refine_inputs.hip.
  * dv_space_to_batch2_f32: [N,C,h,w] -> [4N,C,h/2,w/2]; sub-image (y & 1, x & 1) of item n becomes item 4n + 2(y & 1) + (x & 1)
- *   (h, w even; `in` 8-byte aligned).  A 3x3 convolution with dilation 2d on the input is one with dilation d on the output.
+ *   (h, w even; `in` 8-byte aligned, DV_ERR_ALIGN otherwise).  A 3x3 convolution with dilation 2d on the input is one with dilation d on the output.
  * dv_batch_to_space_f32: the inverse of `levels` such steps at once: in [B * 4^levels, C, H >> levels, W >> levels] -> out [B,C,H,W]. */
 int dv_space_to_batch2_f32(const float* in, float* out, int N, int C, int h, int w, dv_stream_t stream);
 /* dv_conv2d_wino_cat_f32 (dilation 1, no residual / mul / blend) with its output stored through dv_space_to_batch2_f32's
@@ -346,7 +354,8 @@ int dv_feature_gate_bwd_f32(const float* cv /*[B,C,D,H,W]*/, const float* logit 
  *   out = act( deconv3d_k3s2(in, w) + redir_w . skip + ch_bias )
  * Both BatchNorm scales must already be folded into `w` (before dv_deconv3d_pack_weights_f32) and `redir_w`
  * ([Cout][Cskip] row-major, device), their shifts summed into ch_bias.  skip [B,Cskip,2D,2H,2W].
- * Needs W % 2 == 0 and ceil(Cskip/8) <= ceil(Cin/8); otherwise DV_ERR_UNSUPPORTED (run the two layers apart). */
+ * Needs W % 2 == 0, a 16-byte aligned `skip` (its quads must not straddle a row end) and ceil(Cskip/8) <= ceil(Cin/8);
+ * otherwise DV_ERR_UNSUPPORTED (run the two layers apart). */
 int dv_deconv3d_k3s2_redir_f32(const float* in, const float* wpacked, const float* ch_bias, const float* skip,
                                const float* redir_w, float* out, int B, int Cin, int D, int H, int W, int Cout,
                                int Cskip, int act, dv_stream_t stream);
@@ -368,7 +377,8 @@ int dv_patch_volume_runs_f32(const float* gwc, const float* w1, const float* w2,
  * multi-head self-attention (heads x C/heads), qkv Linear(C,3C)+bias, softmax,
  * final 1x1x1 Conv3d(C,C)+bias.  x [B,C,D,H,W] -> out same shape.  D must be a
  * multiple of 4; H,W not multiples of 4 are zero-padded with the reference's
- * -1000 mask rule.  C == 128, heads == 16 in every reference use. */
+ * -1000 mask rule.  C == 128, heads == 16 in every reference use.  qkv_w / proj_w must be 16-byte aligned
+ * (DV_ERR_ALIGN otherwise); x / out and the two bias vectors need not be. */
 int dv_window_attn3d_f32(const float* x, const float* qkv_w /*[3C,C]*/, const float* qkv_b /*[3C]*/,
                          const float* proj_w /*[C,C]*/, const float* proj_b /*[C]*/, float* out,
                          int B, int C, int D, int H, int W, int heads, dv_stream_t stream);
@@ -439,7 +449,7 @@ int dv_ddim_step(const float* disp, const float* unc, const float* used, const f
  * context_upsample (core/submodule.py:241-253):
  *   out[b,Y,X] = sum_{k=3ky+kx} p_k[b,Y,X] * scale * disp_low[b, (Y>>2)+ky-1, (X>>2)+kx-1]   (zeros outside)
  * disp_low [B,h,w]; weights [B,9,4h,4w] (logits when apply_softmax != 0, else probabilities); out [B,4h,4w];
- * scale = 4 in the reference (`disp*4.`).  weights / out must be 16-byte aligned. */
+ * scale = 4 in the reference (`disp*4.`).  weights / out must be 16-byte aligned (DV_ERR_ALIGN otherwise). */
 int dv_context_upsample_f32(const float* disp_low, const float* weights, float* out, int B, int h, int w,
                             float scale, int apply_softmax, dv_stream_t stream);
 
@@ -451,7 +461,8 @@ int dv_context_upsample_f32(const float* disp_low, const float* weights, float* 
  *   d_disp[b,y,x]      = scale * sum_k s_k[b, y-ky+1, x-kx+1],  s_k[cell] = sum over the cell's 16 pixels of g p_k
  * d_weights [B,9,4h,4w] or d_disp [B,h,w] may be NULL (not both): that gradient is not computed.  cell_sums: scratch of
  * B*9*h*w floats (the s_k), required when d_disp is given.  A gather in both passes -- no scatter, no atomics, fixed
- * summation order: the same bits on every launch.  weights / grad_out / d_weights must be 16-byte aligned. */
+ * summation order: the same bits on every launch.  weights / grad_out / d_weights must be 16-byte aligned
+ * (DV_ERR_ALIGN otherwise). */
 int dv_context_upsample_bwd_f32(const float* disp_low, const float* weights, const float* grad_out, float* d_weights,
                                 float* d_disp, float* cell_sums, int B, int h, int w, float scale, int apply_softmax,
                                 dv_stream_t stream);

@@ -6,6 +6,7 @@ of a batch reproduce the batch's bits, shapes it does not take fall back, and th
 import pytest
 import torch
 
+import arena
 from diffuvolume_amd import _lib
 from diffuvolume_amd import submodule as S
 from diffuvolume_amd.synth import _gen
@@ -79,6 +80,19 @@ CASES = [
 ]
 
 
+def _run_into(lib, plan, x, kw, out):
+    """Deconv3dPlan.__call__'s launch into a caller-owned output (the plan allocates its own)."""
+    b, cin, d, h, w = x.shape
+    if "skip" in kw:
+        skip = kw["skip"]
+        return lib.dv_deconv3d_k3s2_redir_f32(x.data_ptr(), plan.wpacked.data_ptr(), _lib.ptr(plan.shift), skip.data_ptr(),
+                                              plan.redir_w.data_ptr(), out.data_ptr(), b, cin, d, h, w, plan.cout, plan.cskip,
+                                              plan.act, _lib.stream_ptr())
+    return lib.dv_deconv3d_k3s2_f32(x.data_ptr(), plan.wpacked.data_ptr(), _lib.ptr(plan.scale), _lib.ptr(plan.shift),
+                                    _lib.ptr(kw.get("residual")), out.data_ptr(), b, cin, d, h, w, plan.cout, plan.act,
+                                    _lib.stream_ptr())
+
+
 @pytest.mark.parametrize("cfg", CASES)
 def test_persistent_vs_torch_and_one_tile(cfg):
     lib = _lib.load()
@@ -93,9 +107,13 @@ def test_persistent_vs_torch_and_one_tile(cfg):
         # the grid must not matter: every output is summed in the same order whichever block computes its tile
         for cap in (1, 3, 8, 13):
             assert lib.dv_deconv3d_pl_set_max_blocks(cap) == 0
-            poison = torch.full_like(out, float("nan"))
-            del poison                                     # the next output lands on these bytes
-            assert torch.equal(plan(x, **kw), out), f"grid of {cap} blocks changes the result"
+            # into an output that holds a sentinel in every word, guard bands included: a tile that no block of the
+            # capped grid reaches, or a store outside the tensor, shows as such (tests/arena.py)
+            dst = arena.place(torch.empty(out.shape), 0, "out", DEV, name=f"out[{cap} blocks]")
+            assert _run_into(lib, plan, x, kw, dst.view) == 0
+            torch.cuda.synchronize()
+            arena.check_output(dst)
+            assert torch.equal(dst.view, out), f"grid of {cap} blocks changes the result"
         lib.dv_deconv3d_pl_set_max_blocks(0)
         assert lib.dv_deconv3d_set_impl(1) == 0
         one_tile = plan(x, **kw)
