@@ -28,6 +28,10 @@ KNOBS = {
     "DV_TRAIN_LOOKUP": ("hip", "geometry_ddim.route() when a training-route volume is built and on each of its lookups",
                         "torch = IGEV's geometry lookup and all-pairs correlation in training as torch expressions (einsum, "
                         "gather) instead of the HIP forward kernels and their HIP backward kernels (A/B runs, tests)"),
+    "DV_TRAIN_TAIL": ("hip", "train_tail.route() on every regression head of ACVNet_DDIM / PWCNet_ddim training",
+                      "torch = the x4 trilinear upsampling + softmax + disparity regression of the training heads as the "
+                      "torch expression (F.interpolate, F.softmax, disparity_regression; atomics in its backward) instead "
+                      "of the fused HIP forward and its atomics-free HIP backward (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

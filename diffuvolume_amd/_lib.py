@@ -1,4 +1,4 @@
-"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h).
+"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h and include/diffuvolume_hip_train.h).
 
 There is deliberately no CPU / eager fallback: if the library is missing or a
 kernel reports an error the call raises.  ``import torch`` happens first so the
@@ -157,6 +157,15 @@ SIGNATURES = {
 }
 
 
+# Second table: training entries declared in include/diffuvolume_hip_train.h (same library, same conventions).  They are
+# kept out of SIGNATURES because every name there must be a row of the inference arena table or an exclusion next to it
+# (tests/test_abi_arena_complete.py); the same decision for these is recorded in tests/test_regress_train_host.py.
+TRAIN_SIGNATURES = {
+    "dv_upsample_softmax_regress_bwd_workspace_floats": (c_size_t, [I, I, I, I]),
+    "dv_upsample_softmax_regress_bwd_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, P]),
+}
+
+
 class DiffuVolumeError(RuntimeError):
     pass
 
@@ -175,7 +184,7 @@ def load() -> ctypes.CDLL:
             f"{_LIB_PATH} is missing: build it with `python -m diffuvolume_amd._build` "
             "(there is no CPU fallback for the DiffuVolume hot path)")
     lib = ctypes.CDLL(os.fspath(_LIB_PATH), mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError => ABI mismatch, also loud
         fn.restype = res
         fn.argtypes = args

@@ -29,11 +29,12 @@ from torch import nn
 
 from . import _lib
 from . import train3d
+from .train_tail import regress_head
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
                         AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
-                        check_split_overflow, default_conv_precision, disparity_regression, patch_volume, upsample_softmax_regress, window_attention)
+                        check_split_overflow, default_conv_precision, patch_volume, upsample_softmax_regress, window_attention)
 
 
 def any_split_plan(plans) -> bool:
@@ -733,14 +734,11 @@ class ACVNet_DDIM(_HipPlanMixin):
 
         size = [self.maxdisp, left.size()[2], left.size()[3]]
 
-        def regress(cost):
-            cost = torch.squeeze(F.interpolate(cost, size, mode="trilinear"), 1)
-            return disparity_regression(F.softmax(cost, dim=1), self.maxdisp)
-
-        pred_attention = regress(att_weights)
-        pred0 = regress(_train_pair(self.classif0, cost0))
-        pred1 = regress(_train_pair(self.classif1, out1))
-        pred2 = regress(_train_pair(self.classif2, out2))
+        # the fused tail with its HIP backward (train_tail.py; DV_TRAIN_TAIL)
+        pred_attention = regress_head(att_weights, size)
+        pred0 = regress_head(_train_pair(self.classif0, cost0), size)
+        pred1 = regress_head(_train_pair(self.classif1, out1), size)
+        pred2 = regress_head(_train_pair(self.classif2, out2), size)
         return [pred_attention, pred0, pred1, pred2]
 
     def forward(self, left, right, used, disp, mask_gt=None):

@@ -6,27 +6,9 @@
 // costs in registers and walks the 4D bins four times (max, sum, expectation, |.| moment),
 // so HBM traffic is the [B,D,h,w] cost in and two [B,4h,4w] maps out.
 #include "dv_common.h"
+#include "regress_tail.h"   // lin_src, tail_shift_bin: shared with the backward (regress_bwd.hip)
 
 namespace {
-
-// PyTorch's linear source index (area_pixel_compute_source_index, non-cubic).
-template <bool ALIGN>
-__device__ __forceinline__ void lin_src(int dst, int in_size, int out_size, int& i0, int& i1, float& l0,
-                                        float& l1) {
-  float src;
-  if (ALIGN) {
-    const float scale = out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    src = scale * (float)dst;
-  } else {
-    const float scale = (float)in_size / (float)out_size;
-    src = scale * ((float)dst + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-  }
-  i0 = (int)src;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
 
 template <int D, bool ALIGN>
 __global__ __launch_bounds__(256) void upsample_softmax_regress_kernel(const float* __restrict__ cost,
@@ -73,16 +55,11 @@ __global__ __launch_bounds__(256) void upsample_softmax_regress_kernel(const flo
     lin_src<ALIGN>((k), D, K, i0_, i1_, l0_, l1_);     \
     (out) = l0_ * c[i0_] + l1_ * c[i1_];               \
   }
-  // Softmax shift = max_k v_k.  Between two neighbouring slices the four bins are a linear ramp, so the maximum sits on
-  // the outer bins of a segment (align_corners=False: k = 4d + 1 and 4d + 2; k = 0 and 4D - 1 are the clamped ends):
-  // half the bins are enough.
-  // (In floating point an inner bin can exceed that by an ulp when the two slices are nearly equal: its exponential is
-  // then 1 + O(ulp), harmless.  The maximum of the 48 SLICES is not a valid shift: bins never reach a slice value, and
-  // with steep costs every exponential would underflow.)
+  // Softmax shift = max_k v_k over the bins of tail_shift_bin (regress_tail.h: half of them without align_corners).
   float m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    if (ALIGN || (k & 3) == 1 || (k & 3) == 2 || k == 0 || k == K - 1) {     // (align_corners=True: bins are not periodic)
+    if (tail_shift_bin<ALIGN>(k, K)) {
       float v;
       DV_VK(k, v);
       m = fmaxf(m, v);

@@ -33,9 +33,10 @@ from torch import nn
 from . import _lib, train2d, train3d
 from .acv_ddim import ProbVolumeHandle, _LoopStep, _bn_of, _plan_cb3, cosine_beta_schedule
 from .head import DynamicHead
+from .train_tail import regress_head
 from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
-                        build_gwc_volume, check_split_overflow, disparity_regression, refine_inputs,
+                        build_gwc_volume, check_split_overflow, refine_inputs,
                         upsample_softmax_regress)
 
 NoiseFn = Callable[[str, Tuple[int, ...], torch.dtype], torch.Tensor]
@@ -906,15 +907,12 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         out3 = self.dres4(out2)
         size = [self.maxdisp, hh, ww]
 
-        def regress(cost):
-            cost = torch.squeeze(F.interpolate(cost, size, mode="trilinear", align_corners=True), 1)
-            return disparity_regression(F.softmax(cost, dim=1), self.maxdisp)
-
-        pred0 = regress(_train_seq(self.classif0, cost0))
-        pred1 = regress(_train_seq(self.classif1, out1))
-        pred2 = regress(_train_seq(self.classif2, out2))
-        pred3 = regress(_train_seq(self.classif3, out3)).unsqueeze(1)
-        pred_combine = regress(_train_seq(self.classif4, combine))
+        # the fused tail with its HIP backward (train_tail.py; DV_TRAIN_TAIL)
+        pred0 = regress_head(_train_seq(self.classif0, cost0), size, align_corners=True)
+        pred1 = regress_head(_train_seq(self.classif1, out1), size, align_corners=True)
+        pred2 = regress_head(_train_seq(self.classif2, out2), size, align_corners=True)
+        pred3 = regress_head(_train_seq(self.classif3, out3), size, align_corners=True).unsqueeze(1)
+        pred_combine = regress_head(_train_seq(self.classif4, combine), size, align_corners=True)
 
         # refinement (:711-728)
         rl, rr = self.refine_features(fl, fr, (hh, ww))
