@@ -32,6 +32,10 @@ KNOBS = {
                       "torch = the x4 trilinear upsampling + softmax + disparity regression of the training heads as the "
                       "torch expression (F.interpolate, F.softmax, disparity_regression; atomics in its backward) instead "
                       "of the fused HIP forward and its atomics-free HIP backward (A/B runs, tests)"),
+    "DV_TRAIN_VOLUME": ("hip", "train_volume.route() on every cost volume ACVNet_DDIM / PWCNet_ddim build while autograd records",
+                        "torch = the group-wise-correlation and concatenation volumes in training as the PyTorch statements "
+                        "of submodule.py (pad / unfold / flip, products, mean, cat) instead of the eval kernels with the "
+                        "atomics-free HIP backward of csrc/volume_bwd.hip (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

@@ -1,4 +1,5 @@
-"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h and include/diffuvolume_hip_train.h).
+"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h, include/diffuvolume_hip_train.h and
+include/diffuvolume_hip_volume_train.h).
 
 There is deliberately no CPU / eager fallback: if the library is missing or a
 kernel reports an error the call raises.  ``import torch`` happens first so the
@@ -166,6 +167,26 @@ TRAIN_SIGNATURES = {
 }
 
 
+# Third table: include/diffuvolume_hip_volume_train.h.  name -> (restype, argtypes, decision): the decision about the
+# entry's pointer and bounds contract sits beside its signature -- SIZE_ONLY, or held_by(<GPU test>) naming the test that
+# calls the entry through offset views, between sentinels and with the arguments it refuses.
+# tests/test_volume_train_host.py reads this table; a later training entry is a row here and a declaration in that header.
+SIZE_ONLY = "only returns a size: launches nothing"
+
+
+def held_by(test: str) -> str:
+    return f"offset views, sentinel-guarded outputs and refusals are held by: {test}"
+
+
+VOLUME_TRAIN_SIGNATURES = {
+    "dv_gwc_volume_bwd_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, I, P],
+                              held_by("test_gpu_volume_train.py::test_gwc_abi_offset_views_bounds_and_refusals")),
+    "dv_concat_volume_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
+    "dv_concat_volume_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+                                 held_by("test_gpu_volume_train.py::test_concat_abi_offset_views_bounds_and_refusals")),
+}
+
+
 class DiffuVolumeError(RuntimeError):
     pass
 
@@ -184,7 +205,8 @@ def load() -> ctypes.CDLL:
             f"{_LIB_PATH} is missing: build it with `python -m diffuvolume_amd._build` "
             "(there is no CPU fallback for the DiffuVolume hot path)")
     lib = ctypes.CDLL(os.fspath(_LIB_PATH), mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **TRAIN_SIGNATURES}.items():
+    tables = {**SIGNATURES, **TRAIN_SIGNATURES, **{k: v[:2] for k, v in VOLUME_TRAIN_SIGNATURES.items()}}
+    for name, (res, args) in tables.items():
         fn = getattr(lib, name)          # AttributeError => ABI mismatch, also loud
         fn.restype = res
         fn.argtypes = args

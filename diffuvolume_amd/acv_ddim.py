@@ -30,6 +30,8 @@ from torch import nn
 from . import _lib
 from . import train3d
 from .train_tail import regress_head
+from . import train_volume
+from .train_volume import build_concat_volume_train
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
@@ -700,16 +702,27 @@ class ACVNet_DDIM(_HipPlanMixin):
 
         cl = self.concatconv(fl)
         cr = self.concatconv(fr)
-        concat_volume = build_concat_volume(cl, cr, self.maxdisp // 4)
-        ac_volume = F.softmax(att_weights, dim=2) * concat_volume
+        # :388-390 `F.softmax(att_weights, dim=2) * concat_volume`, and :451 `* noisy` below, as factors: the softmax on
+        # the [B,1,D,h,w] logits, both products on the [B,D,h,w] scale of build_concat_volume_train.  (p * n) * v instead
+        # of the reference's (p * v) * n: at most one rounding per element, the order of the eval path
+        # DV_TRAIN_VOLUME=torch: the statements as the reference orders them, on the [B,64,D,h,w] tensors
+        factored = train_volume.route() == "hip"
+        p_att = F.softmax(att_weights, dim=2)
+        if not factored:
+            ac_volume = p_att * build_concat_volume(cl, cr, self.maxdisp // 4)
 
         # :384-398 run the aggregation stack once on the un-filtered volume in training mode too; its prediction is
         # overwritten, but the BatchNorm layers of dres0..dres3 / classif2 update their running statistics on it
         with torch.no_grad():
+            if factored:
+                ac_volume = build_concat_volume_train(cl.detach(), cr.detach(), self.maxdisp // 4,
+                                                      scale=p_att.detach()[:, 0])
             cost0 = _train_pair(self.dres0, ac_volume)
             cost0 = _train_pair(self.dres1, cost0) + cost0
             _train_pair(self.classif2, self.dres3(self.dres2(cost0)))
             del cost0
+            if factored:
+                del ac_volume
 
         # two-hot x_start (:426-439), the mask_gt form of the training branch
         x_start = self.encode_disparity(disp.detach().float())
@@ -726,7 +739,10 @@ class ACVNet_DDIM(_HipPlanMixin):
             noisy = ((noisy / self.scale) + 1) / 2.
             noisy = noisy.unsqueeze(1).to(torch.float32)
 
-        ac_volume = ac_volume * noisy
+        if factored:
+            ac_volume = build_concat_volume_train(cl, cr, self.maxdisp // 4, scale=(p_att * noisy)[:, 0])
+        else:
+            ac_volume = ac_volume * noisy
         cost0 = _train_pair(self.dres0, ac_volume)
         cost0 = _train_pair(self.dres1, cost0) + cost0
         out1 = self.dres2(cost0)

@@ -5,9 +5,10 @@ Same names, argument meaning and error behaviour as SceneFlow/models/submodule.p
 ``disparity_regression`` :173-177) and their KITTI12 / KITTI15 twins; the work is
 done by the HIP kernels of libdiffuvolume_hip.so on the current stream.  The three
 builders / the regression are differentiable in the reference (they are used in training):
-when autograd is recording and an input requires grad they dispatch to a differentiable
-PyTorch statement of the same function; everything else is inference only and
-runs on the MI355X or raises.
+when autograd is recording and an input requires grad, the two volume builders dispatch to the
+autograd functions of train_volume.py (eval kernel forward, HIP backward) for CUDA float32
+tensors and to a differentiable PyTorch statement of the same function otherwise (SURVEY 8b);
+everything else is inference only and runs on the MI355X or raises.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, train_volume
 from .profiling import S2PP_MULT_REDUCTION, WINO3_MULT_REDUCTION, WINO_MULT_REDUCTION, timed
 
 __all__ = ["build_gwc_volume", "build_concat_volume", "build_concat_attention_volume", "AttentionConcatVolume",
@@ -88,6 +89,11 @@ def _wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
+def _on_hip_f32(*tensors) -> bool:
+    """CUDA float32 tensors: what the autograd functions of train_volume.py take (their forward is the eval launch)."""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
 def _shift_bank(t: torch.Tensor, maxdisp: int) -> torch.Tensor:
     """[B,C,H,W] -> [B,C,D,H,W] with bank[..., d, y, x] = t[..., y, x - d] (0 where x < d): every disparity shift
     of the target features as one strided view of a left-padded copy (differentiable)."""
@@ -134,6 +140,8 @@ def build_gwc_volume(refimg_fea: torch.Tensor, targetimg_fea: torch.Tensor, maxd
         if refimg_fea.dim() != 4 or refimg_fea.shape != targetimg_fea.shape:
             raise RuntimeError(f"feature shapes differ or are not 4-D: {tuple(refimg_fea.shape)} vs {tuple(targetimg_fea.shape)}")
         assert refimg_fea.shape[1] % num_groups == 0          # submodule.py:211
+        if _on_hip_f32(refimg_fea, targetimg_fea):             # eval kernel + HIP backward (DV_TRAIN_VOLUME)
+            return train_volume.build_gwc_volume_train(refimg_fea, targetimg_fea, maxdisp, num_groups)
         return _gwc_volume_autograd(refimg_fea, targetimg_fea, maxdisp, num_groups)
     ref = _dev_f32(refimg_fea, "refimg_fea")
     tgt = _dev_f32(targetimg_fea, "targetimg_fea")
@@ -160,6 +168,8 @@ def build_concat_volume(refimg_fea: torch.Tensor, targetimg_fea: torch.Tensor, m
     if _wants_grad(refimg_fea, targetimg_fea):
         if refimg_fea.dim() != 4 or refimg_fea.shape != targetimg_fea.shape:
             raise RuntimeError(f"feature shapes differ or are not 4-D: {tuple(refimg_fea.shape)} vs {tuple(targetimg_fea.shape)}")
+        if _on_hip_f32(refimg_fea, targetimg_fea):             # eval kernel + HIP backward (DV_TRAIN_VOLUME)
+            return train_volume.build_concat_volume_train(refimg_fea, targetimg_fea, maxdisp, bool(zero_left))
         return _concat_volume_autograd(refimg_fea, targetimg_fea, maxdisp, bool(zero_left))
     ref = _dev_f32(refimg_fea, "refimg_fea")
     tgt = _dev_f32(targetimg_fea, "targetimg_fea")

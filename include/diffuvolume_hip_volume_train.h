@@ -1,0 +1,62 @@
+/* diffuvolume_hip_volume_train.h -- C ABI of libdiffuvolume_hip.so, third table: the backward of the two cost-volume
+ * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h).
+ *
+ * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
+ * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
+ * training entry is a row of that table and a declaration here.
+ *
+ * Conventions (those of diffuvolume_hip.h)
+ *  - every pointer is a DEVICE pointer to a dense, contiguous row-major tensor in the reference's own layout
+ *    (NCHW / NCDHW); outputs are caller-allocated;
+ *  - nothing here allocates, frees, synchronises or keeps global mutable state; calls are re-entrant and are enqueued on
+ *    `stream` of the current device;
+ *  - alignment: a tensor operand needs only the alignment of its element type (4 bytes for float).  Like the forward
+ *    builders, the entries take 16-byte accesses along W when W % 4 == 0 and every operand lies on a 16-byte line, and a
+ *    one-thread-per-output kernel otherwise: the two agree within rounding (the sums over d run in the same order; the
+ *    sum over c of `ds` is chunked on the fast path), not necessarily in bits;
+ *  - every element of an output is written exactly once, in a fixed summation order, without atomics: the same call gives
+ *    the same bits on every launch, and a batch gives the bits of its items run one by one;
+ *  - a refused call launches nothing and writes nothing;
+ *  - return value: 0 = ok, <0 = DV_ERR_* (bad argument), >0 = hipError_t.
+ */
+#ifndef DIFFUVOLUME_HIP_VOLUME_TRAIN_H
+#define DIFFUVOLUME_HIP_VOLUME_TRAIN_H
+
+#include "diffuvolume_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- group-wise correlation volume, backward -------------------------------------------------------------------------
+ * What autograd computes for build_gwc_volume (SceneFlow/models/submodule.py:209-238) in training.
+ *   ref, tgt [B,C,H,W], dvol [B,G,D,H,W] -> dref, dtgt [B,C,H,W];  cpg = C / G, g = c / cpg
+ *   dref[b,c,y,x]  = (1/cpg) sum_{d<D, d<=x}   dvol[b,g,d,y,x]    tgt[b,c,y,x-d]
+ *   dtgt[b,c,y,x'] = (1/cpg) sum_{d<D, x'+d<W} dvol[b,g,d,y,x'+d] ref[b,c,y,x'+d]
+ * Either output may be NULL (a frozen side costs nothing); both NULL: DV_ERR_NULL.  C % G != 0: DV_ERR_SHAPE. */
+int dv_gwc_volume_bwd_f32(const float* ref, const float* tgt, const float* dvol, float* dref, float* dtgt, int B, int C,
+                          int H, int W, int D, int G, dv_stream_t stream);
+
+/* ---- concatenation volume, backward ----------------------------------------------------------------------------------
+ * What autograd computes for build_concat_volume (SceneFlow/models/submodule.py:180-191; KITTI12/models/submodule.py:86-97
+ * with zero_left) and for a scale s[b,d,y,x] multiplied onto it (the softmax(att) * volume * noisy of
+ * SceneFlow/models/acv_ddim.py:694-704), i.e. for the forward
+ *   vol[b,c,d,y,x] = s ref[b,c,y,x]   (0 for x < d with zero_left),   vol[b,C+c,d,y,x] = s tgt[b,c,y,x-d]   (0 for x < d)
+ *   ref, tgt [B,C,H,W], s [B,D,H,W] or NULL (= 1), dvol [B,2C,D,H,W] -> dref, dtgt [B,C,H,W], ds [B,D,H,W]
+ *   dref[b,c,y,x]  = sum_d s dvol[b,c,d,y,x]                                       (d <= x only with zero_left)
+ *   dtgt[b,c,y,x'] = sum_{d, x'+d<W} s[b,d,y,x'+d] dvol[b,C+c,d,y,x'+d]
+ *   ds[b,d,y,x]    = sum_c dvol[b,c,d,y,x] ref[b,c,y,x] + [x>=d] sum_c dvol[b,C+c,d,y,x] tgt[b,c,y,x-d]
+ * Each output may be NULL; all three NULL: DV_ERR_NULL.  ref / tgt are read only for ds and may be NULL without it.
+ * ds without s: DV_ERR_NULL.  s together with zero_left: DV_ERR_UNSUPPORTED (dv_concat_prob_volume_f32 has no such
+ * forward).  On the fast path ds is summed over chunks of 8 channels in `workspace`
+ * (dv_concat_volume_bwd_workspace_floats floats, [chunks][B,D,H,W]) and then over the chunks in ascending order;
+ * `workspace` is required (DV_ERR_NULL) when ds is wanted and that size is not 0, and may be NULL otherwise. */
+size_t dv_concat_volume_bwd_workspace_floats(int B, int C, int H, int W, int D);
+int dv_concat_volume_bwd_f32(const float* ref, const float* tgt, const float* s, const float* dvol, float* dref,
+                             float* dtgt, float* ds, float* workspace, int B, int C, int H, int W, int D, int zero_left,
+                             dv_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DIFFUVOLUME_HIP_VOLUME_TRAIN_H */
