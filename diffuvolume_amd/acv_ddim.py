@@ -19,15 +19,15 @@ Training (``model.train()``, the reference's :424-482 branch): ``forward`` retur
 """
 from __future__ import annotations
 
-import ctypes
 import math
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from . import ddim
 from . import train3d
 from .train_tail import regress_head
 from . import train_volume
@@ -43,7 +43,6 @@ def any_split_plan(plans) -> bool:
     """True if the prepared layers include a split-fp16 convolution (its range guard must be read)."""
     return plans is not None and getattr(plans.dres0.b, "split", False)
 
-NoiseFn = Callable[[str, Tuple[int, ...], torch.dtype], torch.Tensor]
 
 
 # --------------------------------------------------------------------------------------
@@ -314,12 +313,8 @@ class _Plans:
         self.patch_dil = torch.tensor([1] * 8 + [2] * 16 + [3] * 16, dtype=torch.int32, device=self.patch_w1.device)
         self.concat_a = _plan_cb2(m.concatconv[0], ACT_RELU)
         self.concat_b = Conv2dPlan(m.concatconv[2].weight, None, act=ACT_NONE)
-        if hasattr(m, "alphas_cumprod"):                       # the origin ACVNet has no diffusion schedule
-            ac = m.alphas_cumprod.detach().double().cpu()
-            self.alphas_cumprod = ac
-            self.sqrt_recip = torch.sqrt(1.0 / ac)
-            self.sqrt_recipm1 = torch.sqrt(1.0 / ac - 1)
-        self.loop_key = self.loop_steps = None          # per-step constants of the DDIM loop (ACVNet_DDIM._loop_plan)
+        # the origin ACVNet has no diffusion schedule
+        self.ddim = ddim.Tables(m.alphas_cumprod) if hasattr(m, "alphas_cumprod") else None
 
 
 def _volume_arg(volume):
@@ -329,20 +324,6 @@ def _volume_arg(volume):
 
 def _volume_tensor(volume) -> torch.Tensor:
     return volume.tensor() if isinstance(volume, AttentionConcatVolume) else volume
-
-
-class _LoopStep:
-    """Everything one DDIM step needs that depends only on its timestep: the coefficient struct handed to
-    ``dv_ddim_step`` by value and the time-MLP shift (device resident; one row per batch entry on demand)."""
-
-    def __init__(self, time: int, time_next: int, coef: "_lib.DvDdimCoef", shift: torch.Tensor):
-        self.time, self.time_next, self.coef, self.shift = time, time_next, coef, shift
-        self._rows = {}
-
-    def shift_rows(self, b: int) -> torch.Tensor:
-        if b not in self._rows:
-            self._rows[b] = self.shift.reshape(1, -1).expand(b, -1).contiguous()
-        return self._rows[b]
 
 
 class ProbVolumeHandle:
@@ -358,14 +339,6 @@ class ProbVolumeHandle:
         up = F.interpolate(self.cost, [self.maxdisp, h * 4, w * 4], mode="trilinear",
                            align_corners=True if self.align_corners else None)
         return F.softmax(up.squeeze(1), dim=1)
-
-
-def cosine_beta_schedule(timesteps: int, s: float = 0.008) -> torch.Tensor:
-    """acv_ddim.py:113-119 (float64)."""
-    x = torch.linspace(0, timesteps, timesteps + 1, dtype=torch.float64)
-    ac = torch.cos(((x / timesteps) + s) / (1 + s) * math.pi * 0.5) ** 2
-    ac = ac / ac[0]
-    return torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999)
 
 
 class _HipPlanMixin(PlanCache, nn.Module):
@@ -407,22 +380,7 @@ class ACVNet_DDIM(_HipPlanMixin):
         self.ensemble_cof = tuple(float(c) for c in ensemble_cof)
         self.dif_threshold, self.unc_threshold = 1.0, 3.0
 
-        betas = cosine_beta_schedule(self.num_timesteps)
-        alphas = 1.0 - betas
-        ac = torch.cumprod(alphas, dim=0)
-        ac_prev = F.pad(ac[:-1], (1, 0), value=1.0)
-        post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
-        for name, val in (("betas", betas), ("alphas_cumprod", ac), ("alphas_cumprod_prev", ac_prev),
-                          ("sqrt_alphas_cumprod", torch.sqrt(ac)),
-                          ("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - ac)),
-                          ("log_one_minus_alphas_cumprod", torch.log(1.0 - ac)),
-                          ("sqrt_recip_alphas_cumprod", torch.sqrt(1.0 / ac)),
-                          ("sqrt_recipm1_alphas_cumprod", torch.sqrt(1.0 / ac - 1)),
-                          ("posterior_variance", post_var),
-                          ("posterior_log_variance_clipped", torch.log(post_var.clamp(min=1e-20))),
-                          ("posterior_mean_coef1", betas * torch.sqrt(ac_prev) / (1.0 - ac)),
-                          ("posterior_mean_coef2", (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac))):
-            self.register_buffer(name, val)
+        ddim.register_schedule(self, self.num_timesteps)
 
         self.feature_extraction = FeatureExtraction()
         self.concatconv = nn.Sequential(_cb2(320, 128, 3, 1, 1, 1), nn.ReLU(inplace=True),
@@ -464,31 +422,11 @@ class ACVNet_DDIM(_HipPlanMixin):
                 m.bias.data.zero_()
 
     # ---- pieces of the hot path ----------------------------------------------------------
-    def _time_pairs(self) -> List[Tuple[int, int]]:
-        times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
-        times = list(reversed(times.int().tolist()))
-        return list(zip(times[:-1], times[1:]))
+    def _time_pairs(self):
+        return ddim.time_pairs(self.num_timesteps, self.sampling_timesteps)
 
     def _filter(self, x_t: torch.Tensor, t: Optional[torch.Tensor], shift: Optional[torch.Tensor] = None):
-        """time shift + clamp + [0,1] (head.py:74-77, acv_ddim.py:256-258) -> (n01 state dtype, n01 fp32).
-        ``shift`` [B,48]: the time MLP's output when it was precomputed for this step (``_loop_plan``)."""
-        b, c, h, w = x_t.shape
-        if shift is None:
-            shift = self.time_embedding.shift(t).float().contiguous()
-        lib = _lib.load()
-        x_t = x_t.contiguous()
-        if x_t.dtype == torch.float32:
-            n01 = torch.empty_like(x_t)
-            _lib.check(lib.dv_noise_prepare_f32(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), b, c, h * w,
-                                                _lib.stream_ptr()), "dv_noise_prepare_f32")
-            return n01, n01
-        if x_t.dtype != torch.float64:
-            raise TypeError("the DDIM state is float32 (first step) or float64")
-        n01 = torch.empty_like(x_t)
-        n01f = torch.empty(x_t.shape, dtype=torch.float32, device=x_t.device)
-        _lib.check(lib.dv_noise_prepare_f64(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), n01f.data_ptr(),
-                                            b, c, h * w, _lib.stream_ptr()), "dv_noise_prepare_f64")
-        return n01, n01f
+        return ddim.noise_prepare(self.time_embedding, x_t, t, shift)
 
     def _aggregate(self, volume: torch.Tensor, n01f: Optional[torch.Tensor]) -> torch.Tensor:
         """acv_ddim.py:260-266: (volume * filter) -> dres0 -> dres1(+res) -> dres2 -> dres3 -> classif2."""
@@ -503,67 +441,12 @@ class ACVNet_DDIM(_HipPlanMixin):
         return p.classif2(out2)
 
     def _step_coef(self, time: int, time_next: int, cof: float) -> _lib.DvDdimCoef:
-        p = self.prepare()
-        k = _lib.DvDdimCoef()
-        k.sqrt_recip_alpha = float(p.sqrt_recip[time])
-        k.sqrt_recipm1_alpha = float(p.sqrt_recipm1[time])
-        k.dif_thr, k.unc_thr, k.cof = self.dif_threshold, self.unc_threshold, cof
-        k.last = int(time_next < 0)
-        k.clamp_max, k.ens_dif_thr = float(self.maxdisp - 1), 0.0
-        if time_next >= 0:
-            alpha, alpha_next = p.alphas_cumprod[time], p.alphas_cumprod[time_next]
-            sigma = self.ddim_sampling_eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-            k.sigma = float(sigma)
-            k.c = float((1 - alpha_next - sigma ** 2).sqrt())
-            k.sqrt_alpha_next = float(alpha_next.sqrt())
-        return k
+        return ddim.step_coef(self.prepare().ddim, time, time_next, cof, eta=self.ddim_sampling_eta,
+                              dif_thr=self.dif_threshold, unc_thr=self.unc_threshold,
+                              clamp_max=float(self.maxdisp - 1), ens_dif_thr=0.0)
 
-    def _loop_plan(self) -> List[_LoopStep]:
-        """Per-step constants of ``ddim_sample`` (acv_ddim.py:306-308, :348-352 and the time MLP of head.py:74-75,
-        which sees nothing but ``t``): computed once per (weights, step list) and kept on the device, so the loop
-        itself launches no time-MLP kernels and copies no scalars."""
-        p = self.prepare()
-        key = (self.sampling_timesteps, self.ensemble_cof, self.dif_threshold, self.unc_threshold,
-               self.ddim_sampling_eta, self.num_timesteps)
-        if p.loop_key != key:
-            dev = self.dres0[0][0].weight.device
-            steps = []
-            for i, (time, time_next) in enumerate(self._time_pairs()):
-                t = torch.full((1,), time, device=dev, dtype=torch.long)
-                shift = self.time_embedding.shift(t).float().reshape(-1).contiguous()
-                steps.append(_LoopStep(time, time_next, self._step_coef(time, time_next, self.ensemble_cof[i + 1]), shift))
-            p.loop_steps, p.loop_key = steps, key
-        return p.loop_steps
-
-    def _ddim_update(self, disp, unc, used, n01, eps, fill, mask, ens, coef, want_pred_noise=False):
-        b, c, h, w = n01.shape
-        dev = disp.device
-        x_start = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
-        x_next = None if coef.last else torch.empty((b, c, h, w), dtype=torch.float64, device=dev)
-        pred_noise = torch.empty((b, c, h, w), dtype=torch.float64, device=dev) if want_pred_noise else None
-        f32 = n01.dtype == torch.float32
-        eps32 = eps if (eps is not None and eps.dtype == torch.float32) else None
-        eps64 = eps if (eps is not None and eps.dtype == torch.float64) else None
-        lib = _lib.load()
-        _lib.check(lib.dv_ddim_step(disp.data_ptr(), unc.data_ptr(), used.data_ptr(), 0,
-                                    n01.data_ptr() if f32 else 0, 0 if f32 else n01.data_ptr(),
-                                    _lib.ptr(eps32), _lib.ptr(eps64), _lib.ptr(fill), mask.data_ptr(),
-                                    x_start.data_ptr(), _lib.ptr(pred_noise), _lib.ptr(x_next), _lib.ptr(ens),
-                                    b, c, h, w, ctypes.byref(coef), _lib.stream_ptr()), "dv_ddim_step")
-        return x_start, x_next, pred_noise
-
-    def _check_loop_args(self, volume, used, img):
-        """Shapes the kernels index by: used / disp / ens are [B,4h,4w] for a [B,C,48,h,w] volume (the reference
-        fails with a broadcast error at ``disp - used``, acv_ddim.py:322)."""
-        b, _, d, h, w = volume.shape
-        if d != self.maxdisp // 4:
-            raise RuntimeError(f"the volume must have {self.maxdisp // 4} disparity bins, got {d}")
-        if used.numel() != b * 16 * h * w or tuple(used.shape[-2:]) != (4 * h, 4 * w):
-            raise RuntimeError(f"The size of tensor a {(b, 4 * h, 4 * w)} must match the size of tensor b "
-                               f"{tuple(used.shape)}: `used` must be the full-resolution disparity of the volume")
-        if tuple(img.shape) != (b, d, h, w):
-            raise RuntimeError(f"x_T must be {(b, d, h, w)}, got {tuple(img.shape)}")
-        return used.reshape(b, 4 * h, 4 * w)
+    def _loop_plan(self):
+        return ddim.loop_plan(self, self.prepare().ddim, self.dres0[0][0].weight.device)
 
     # ---- reference API ---------------------------------------------------------------------
     @torch.no_grad()
@@ -579,8 +462,8 @@ class ACVNet_DDIM(_HipPlanMixin):
             time = int(t.reshape(-1)[0])
             coef = self._step_coef(time, -1, 0.0)
             mask = torch.zeros((b, h, w), dtype=torch.float32, device=volume.device)
-            x_start, _, pred_noise = self._ddim_update(pred, unc, pred, n01, None, None, mask, None, coef,
-                                                       want_pred_noise=True)
+            x_start, _, pred_noise = ddim.ddim_update(pred, pred, n01, None, None, mask, None, coef, unc=unc,
+                                                      want_pred_noise=True)
         return pred_noise, x_start, pred, ProbVolumeHandle(cost, unc, self.maxdisp)
 
     @torch.no_grad()
@@ -597,28 +480,23 @@ class ACVNet_DDIM(_HipPlanMixin):
         n01, n01f = self._filter(img, None, st.shift_rows(b))
         cost = self._aggregate(volume, n01f)
         disp, unc = upsample_softmax_regress(cost, want_uncertainty=True, out_disp=out_disp)
-        x_start, x_next, _ = self._ddim_update(disp, unc, used, n01, eps, fill, mask, ens, st.coef)
+        x_start, x_next, _ = ddim.ddim_update(disp, used, n01, eps, fill, mask, ens, st.coef, unc=unc)
         return disp, unc, x_start, x_next
 
     @torch.no_grad()
     def ddim_sample(self, volume: torch.Tensor, used: torch.Tensor, asd: torch.Tensor,
-                    noise: Optional[NoiseFn] = None, generator: Optional[torch.Generator] = None,
+                    noise: Optional[ddim.NoiseFn] = None, generator: Optional[torch.Generator] = None,
                     trace: Optional[Callable[[int, dict], None]] = None):
         """acv_ddim.py:298-370.  ``noise(kind, shape, dtype)`` (kind 'eps' = randn_like(img) :354,
         'fill' = rand_like :360) injects the random draws for parity tests; by default they come
         from the device generator.  ``trace(i, state)`` (tests) receives every step's tensors.
         Returns (final_prediction [B,H,W], stack [S+1,B,H,W])."""
         volume = _volume_arg(volume)
-        used = self._check_loop_args(volume, _dev_f32(used, "used"), asd)
+        used = ddim.check_loop_args(volume, _dev_f32(used, "used"), asd, self.maxdisp)
         b, _, d, h, w = volume.shape
         dev = volume.device
         self.prepare(check_weights=True)
-
-        def draw(kind, shape, dtype):
-            if noise is not None:
-                return noise(kind, shape, dtype).to(device=dev, dtype=dtype).contiguous()
-            fn = torch.randn if kind == "eps" else torch.rand
-            return fn(shape, device=dev, dtype=dtype, generator=generator)
+        draw = ddim.make_draw(noise, generator, dev)
 
         with torch.cuda.device(dev):
             steps = self._loop_plan()
@@ -652,12 +530,8 @@ class ACVNet_DDIM(_HipPlanMixin):
         at every call site of the reference; anything that broadcasts against [B,48,h,w]) puts the uniform distribution
         1/48 where it is 0 (:415-417)."""
         disp = _dev_f32(disp, "disp")
-        b, h, w = disp.shape[0], disp.shape[-2], disp.shape[-1]
         nb = self.maxdisp // 4
-        x = torch.empty((b, nb, h, w), dtype=torch.float32, device=disp.device)
-        with torch.cuda.device(disp.device):
-            _lib.check(_lib.load().dv_encode_two_hot_f32(disp.data_ptr(), x.data_ptr(), b, nb, h * w,
-                                                         _lib.stream_ptr()), "dv_encode_two_hot_f32")
+        x = ddim.encode_two_hot(disp, nb)
         if mask_gt is not None:
             # the reference selects before the *2-1 rescale; the same fp32 operations on the one constant it selects
             uniform = ((torch.ones((), dtype=torch.float32, device=x.device) / nb) * 2 - 1) * self.scale

@@ -10,7 +10,6 @@ IGEVStereo_ddim binds its own, a test may bind an oracle's.  Batch handling: the
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Callable, Optional, Sequence
 
@@ -18,8 +17,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
-from .acv_ddim import cosine_beta_schedule
+from . import ddim
 from .head import SinusoidalPositionEmbeddings
 from .submodule import _dev_f32
 
@@ -67,30 +65,14 @@ class IGEVDiffusionLoop:
         self.mixed_precision = bool(mixed_precision)     # the update block under fp16 autocast (igev_stereo_ddim.py:242)
         self.num_timesteps, self.sampling_timesteps, self.eta = 1000, sampling_timesteps, 1.0
         self.ensemble_cof = tuple(float(c) for c in ensemble_cof)
-        ac = torch.cumprod(1.0 - cosine_beta_schedule(1000), dim=0)
-        self.alphas_cumprod = ac
-        self.sqrt_ac, self.sqrt_1mac = torch.sqrt(ac), torch.sqrt(1.0 - ac)
-        self.sqrt_recip, self.sqrt_recipm1 = torch.sqrt(1.0 / ac), torch.sqrt(1.0 / ac - 1)
+        # the loop holds no module: the schedule as constructed, not a checkpoint's `alphas_cumprod` buffer (ddim.Tables)
+        self.tables = ddim.Tables(torch.cumprod(1.0 - ddim.cosine_beta_schedule(1000), dim=0))
 
     def _time_pairs(self):
-        times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
-        times = list(reversed(times.int().tolist()))
-        return list(zip(times[:-1], times[1:]))
+        return ddim.time_pairs(self.num_timesteps, self.sampling_timesteps)
 
     def _filter(self, x_t, t):
-        b, c, h, w = x_t.shape
-        shift = self.time_embedding.shift(t).float().contiguous()
-        lib = _lib.load()
-        x_t = x_t.contiguous()
-        n01 = torch.empty_like(x_t)
-        if x_t.dtype == torch.float32:
-            _lib.check(lib.dv_noise_prepare_f32(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), b, c, h * w,
-                                                _lib.stream_ptr()), "dv_noise_prepare_f32")
-            return n01, n01
-        n01f = torch.empty(x_t.shape, dtype=torch.float32, device=x_t.device)
-        _lib.check(lib.dv_noise_prepare_f64(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), n01f.data_ptr(), b, c,
-                                            h * w, _lib.stream_ptr()), "dv_noise_prepare_f64")
-        return n01, n01f
+        return ddim.noise_prepare(self.time_embedding, x_t, t)
 
     # ---- the GRU iterations of one DDIM step as a hipGraph -------------------------------------------------------
     # One step launches `iters` x ~30 small kernels (1/8- and 1/16-scale convolutions of 0.06-0.1 ms) from Python through
@@ -171,31 +153,13 @@ class IGEVDiffusionLoop:
         return flow_up, coords1, net_list
 
     def _coef(self, time, time_next, cof):
-        k = _lib.DvDdimCoef()
-        k.sqrt_recip_alpha, k.sqrt_recipm1_alpha = float(self.sqrt_recip[time]), float(self.sqrt_recipm1[time])
-        k.dif_thr, k.unc_thr, k.cof, k.last = 5.0, float("inf"), cof, int(time_next < 0)
-        k.clamp_max, k.ens_dif_thr = 47.0, 3.0        # clamp(pred, 0, 48-1) :265; output rule dif<3 :323-327
-        if time_next >= 0:
-            alpha, alpha_next = self.alphas_cumprod[time], self.alphas_cumprod[time_next]
-            sigma = self.eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-            k.sigma, k.c, k.sqrt_alpha_next = float(sigma), float((1 - alpha_next - sigma ** 2).sqrt()), float(alpha_next.sqrt())
-        return k
+        # renewal mask dif < 5 without an uncertainty test; clamp(pred, 0, 48-1) :265; output rule dif < 3 :323-327
+        return ddim.step_coef(self.tables, time, time_next, cof, eta=self.eta, dif_thr=5.0, unc_thr=float("inf"),
+                              clamp_max=47.0, ens_dif_thr=3.0)
 
     def _update(self, pred, used, coords0, n01, eps, fill, mask, ens, coef, want_pred_noise=False):
-        b, c, h, w = n01.shape
-        dev = pred.device
-        x_start = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
-        x_next = None if coef.last else torch.empty((b, c, h, w), dtype=torch.float64, device=dev)
-        pn = torch.empty((b, c, h, w), dtype=torch.float64, device=dev) if want_pred_noise else None
-        f32 = n01.dtype == torch.float32
-        e32 = eps if (eps is not None and eps.dtype == torch.float32) else None
-        e64 = eps if (eps is not None and eps.dtype == torch.float64) else None
-        _lib.check(_lib.load().dv_ddim_step(pred.data_ptr(), 0, used.data_ptr(), coords0.data_ptr(),
-                                            n01.data_ptr() if f32 else 0, 0 if f32 else n01.data_ptr(),
-                                            _lib.ptr(e32), _lib.ptr(e64), _lib.ptr(fill), mask.data_ptr(),
-                                            x_start.data_ptr(), _lib.ptr(pn), _lib.ptr(x_next), _lib.ptr(ens),
-                                            b, c, h, w, ctypes.byref(coef), _lib.stream_ptr()), "dv_ddim_step")
-        return x_start, x_next, pn
+        return ddim.ddim_update(pred, used, n01, eps, fill, mask, ens, coef, coords0=coords0,
+                                want_pred_noise=want_pred_noise)
 
     @torch.no_grad()
     def model_predictions(self, coords0, coords1, flow_init, iters, net_list, inp_list, corr_fn, noise, t, stem_2x):
@@ -220,12 +184,7 @@ class IGEVDiffusionLoop:
         b, d, h, w = asd.shape
         dev = asd.device
         used2 = _dev_f32(used, "used").reshape(b, 4 * h, 4 * w)
-
-        def draw(kind, shape, dtype):
-            if noise is not None:
-                return noise(kind, shape, dtype).to(device=dev, dtype=dtype).contiguous()
-            return torch.randn(shape, device=dev, dtype=dtype, generator=generator)
-
+        draw = ddim.make_draw(noise, generator, dev)
         img = draw("x_T", tuple(asd.shape), torch.float32)
         mask = torch.zeros((b, h, w), dtype=torch.float32, device=dev)
         ens = used2 * self.ensemble_cof[0]
@@ -233,8 +192,7 @@ class IGEVDiffusionLoop:
             eps = fill = None
             if time_next >= 0:
                 eps = draw("eps", tuple(img.shape), img.dtype)
-                fill = (self.sqrt_ac[time].item() * asd.double()
-                        + self.sqrt_1mac[time].item() * draw("q", tuple(asd.shape), asd.dtype).double()).contiguous()
+                fill = self.tables.q_fill(time, asd, draw("q", tuple(asd.shape), asd.dtype)).contiguous()
             _, x_start, x_next, coords1, net_list = self.ddim_step(i, coords0, coords1, flow_init, iters, net_list, inp_list,
                                                                    corr_fn, used2, img, mask, ens, eps, fill, stem_2x)
             img = x_start if time_next < 0 else x_next

@@ -16,18 +16,14 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from .ddim import SCHEDULE_BUFFERS
 from .igev_stereo_ddim import IGEVStereo_ddim, context_upsample, hip_sequential, round_gru_inputs_f16
-
-_SCHEDULE = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
-             "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
-             "posterior_variance", "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2")
-
 
 class IGEVStereo(IGEVStereo_ddim):
     def __init__(self, args, feature: Optional[nn.Module] = None, cnet: Optional[nn.Module] = None):
         super().__init__(args, feature=feature, cnet=cnet)
         del self.time_embedding                          # igev_stereo.py:91-135 has neither the time MLP ...
-        for name in _SCHEDULE:                           # ... nor the diffusion schedule
+        for name in SCHEDULE_BUFFERS:                    # ... nor the diffusion schedule
             del self._buffers[name]
 
     def forward(self, image1, image2, iters=12, flow_init=None, test_mode=False):

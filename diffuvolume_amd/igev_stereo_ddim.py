@@ -13,11 +13,9 @@ from __future__ import annotations
 from typing import Optional, Sequence
 
 import torch
-import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
-from .acv_ddim import cosine_beta_schedule
+from . import _lib, ddim
 from .igev_front2d import Feature, MultiBasicEncoder, _front2d
 from .igev_layers import (HIP, TRAIN, BasicConv, BasicConv_IN, Conv2x, Conv2x_IN, _Conv2xBase, _FewInPlan,  # noqa: F401
                           _PLAN_CACHE, _bn_tuple, _require_cuda, _stem, _train_mode, _wants_autograd, freeze_bn)
@@ -76,22 +74,7 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
                 raise ValueError("give ensemble_cof (S+1 weights) when sampling_timesteps != 2")
             ensemble_cof = (0.6, 0.1, 0.3)
         self.ensemble_cof = tuple(float(c) for c in ensemble_cof)
-        betas = cosine_beta_schedule(self.num_timesteps)
-        alphas = 1.0 - betas
-        ac = torch.cumprod(alphas, dim=0)
-        ac_prev = F.pad(ac[:-1], (1, 0), value=1.0)
-        post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
-        for name, val in (("betas", betas), ("alphas_cumprod", ac), ("alphas_cumprod_prev", ac_prev),
-                          ("sqrt_alphas_cumprod", torch.sqrt(ac)),
-                          ("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - ac)),
-                          ("log_one_minus_alphas_cumprod", torch.log(1.0 - ac)),
-                          ("sqrt_recip_alphas_cumprod", torch.sqrt(1.0 / ac)),
-                          ("sqrt_recipm1_alphas_cumprod", torch.sqrt(1.0 / ac - 1)),
-                          ("posterior_variance", post_var),
-                          ("posterior_log_variance_clipped", torch.log(post_var.clamp(min=1e-20))),
-                          ("posterior_mean_coef1", betas * torch.sqrt(ac_prev) / (1.0 - ac)),
-                          ("posterior_mean_coef2", (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac))):
-            self.register_buffer(name, val)
+        ddim.register_schedule(self, self.num_timesteps)
 
         from .update import BasicMultiUpdateBlock
         hidden = list(args.hidden_dims)
@@ -162,12 +145,7 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
     def encode_disparity(self, flow_gt):
         """:405-419: two-hot x_0 of the quarter-resolution origin disparity, clamped to [0, 47]."""
         dq = torch.clamp(_dev_f32(flow_gt, "flow_gt"), 0, 47).contiguous()
-        b, h, w = dq.shape[0], dq.shape[-2], dq.shape[-1]
-        x = torch.empty((b, 48, h, w), dtype=torch.float32, device=dq.device)
-        with torch.cuda.device(dq.device):
-            _lib.check(_lib.load().dv_encode_two_hot_f32(dq.data_ptr(), x.data_ptr(), b, 48, h * w, _lib.stream_ptr()),
-                       "dv_encode_two_hot_f32")
-        return x
+        return ddim.encode_two_hot(dq, 48)
 
     def _front(self, image1, image2):
         """:364-400 up to the GRU inputs: feature pyramid + stems, matching features, cost volume + initial disparity,

@@ -22,24 +22,21 @@ correlation, ``dispupsample`` in float64) on PyTorch autograd; on CPU tensors it
 """
 from __future__ import annotations
 
-import ctypes
 import math
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, train2d, train3d
-from .acv_ddim import ProbVolumeHandle, _LoopStep, _bn_of, _plan_cb3, cosine_beta_schedule
+from . import _lib, ddim, train2d, train3d
+from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
 from .head import DynamicHead
 from .train_tail import regress_head
 from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, refine_inputs,
                         upsample_softmax_regress)
-
-NoiseFn = Callable[[str, Tuple[int, ...], torch.dtype], torch.Tensor]
 
 
 class Mish(nn.Module):
@@ -485,12 +482,8 @@ class _Plans:
         g = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().float()
         self.du_a = (conv.weight.detach().float().reshape(-1) * g).contiguous()
         self.du_b = (bn.bias.detach().float() - bn.running_mean.detach().float() * g).contiguous()
-        if hasattr(m, "alphas_cumprod"):                                  # the origin network has no schedule
-            ac = m.alphas_cumprod.detach().double().cpu()
-            self.alphas_cumprod = ac
-            self.sqrt_ac, self.sqrt_1mac = torch.sqrt(ac), torch.sqrt(1.0 - ac)
-            self.sqrt_recip, self.sqrt_recipm1 = torch.sqrt(1.0 / ac), torch.sqrt(1.0 / ac - 1)
-        self.loop_key = self.loop_steps = None          # per-step constants of the DDIM loop (PWCNet_ddim._loop_plan)
+        # the origin network has no schedule
+        self.ddim = ddim.Tables(m.alphas_cumprod) if hasattr(m, "alphas_cumprod") else None
 
 
 def groupwise_corr_pm(ref: torch.Tensor, tgt: torch.Tensor, maxdisp: int) -> torch.Tensor:
@@ -656,63 +649,18 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         self.ensemble_cof = tuple(float(c) for c in ensemble_cof)
         self.dif_threshold, self.unc_threshold = 1.0, 1.0            # :571-572 (the last step's <2 mask is unused)
 
-        betas = cosine_beta_schedule(self.num_timesteps)
-        alphas = 1.0 - betas
-        ac = torch.cumprod(alphas, dim=0)
-        ac_prev = F.pad(ac[:-1], (1, 0), value=1.0)
-        post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
-        for name, val in (("betas", betas), ("alphas_cumprod", ac), ("alphas_cumprod_prev", ac_prev),
-                          ("sqrt_alphas_cumprod", torch.sqrt(ac)),
-                          ("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - ac)),
-                          ("log_one_minus_alphas_cumprod", torch.log(1.0 - ac)),
-                          ("sqrt_recip_alphas_cumprod", torch.sqrt(1.0 / ac)),
-                          ("sqrt_recipm1_alphas_cumprod", torch.sqrt(1.0 / ac - 1)),
-                          ("posterior_variance", post_var),
-                          ("posterior_log_variance_clipped", torch.log(post_var.clamp(min=1e-20))),
-                          ("posterior_mean_coef1", betas * torch.sqrt(ac_prev) / (1.0 - ac)),
-                          ("posterior_mean_coef2", (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac))):
-            self.register_buffer(name, val)
-
+        ddim.register_schedule(self, self.num_timesteps)
         self._init_backbone(use_concat_volume, time_embedding=True)
 
-    def _loop_plan(self):
-        """Per-step constants of the loop (time-MLP shift on the device, coefficient struct): they depend only
-        on the step list, so they are computed once per weight set instead of once per step and pass."""
-        p = self.prepare()
-        key = (self.sampling_timesteps, self.ensemble_cof, self.dif_threshold, self.unc_threshold,
-               self.ddim_sampling_eta, self.num_timesteps)
-        if p.loop_key != key:
-            dev = self.dres0[0][0].weight.device
-            steps = []
-            for i, (time, time_next) in enumerate(self._time_pairs()):
-                t = torch.full((1,), time, device=dev, dtype=torch.long)
-                shift = self.time_embedding.shift(t).float().reshape(-1).contiguous()
-                steps.append(_LoopStep(time, time_next, self._step_coef(time, time_next, self.ensemble_cof[i + 1]), shift))
-            p.loop_steps, p.loop_key = steps, key
-        return p.loop_steps
-
     # ---- pieces ---------------------------------------------------------------------------------------
+    def _loop_plan(self):
+        return ddim.loop_plan(self, self.prepare().ddim, self.dres0[0][0].weight.device)
+
     def _time_pairs(self):
-        times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
-        times = list(reversed(times.int().tolist()))
-        return list(zip(times[:-1], times[1:]))
+        return ddim.time_pairs(self.num_timesteps, self.sampling_timesteps)
 
     def _filter(self, x_t, t, shift=None):
-        b, c, h, w = x_t.shape
-        if shift is None:
-            shift = self.time_embedding.shift(t).float().contiguous()
-        lib = _lib.load()
-        x_t = x_t.contiguous()
-        if x_t.dtype == torch.float32:
-            n01 = torch.empty_like(x_t)
-            _lib.check(lib.dv_noise_prepare_f32(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), b, c, h * w,
-                                                _lib.stream_ptr()), "dv_noise_prepare_f32")
-            return n01, n01
-        n01 = torch.empty_like(x_t)
-        n01f = torch.empty(x_t.shape, dtype=torch.float32, device=x_t.device)
-        _lib.check(lib.dv_noise_prepare_f64(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), n01f.data_ptr(),
-                                            b, c, h * w, _lib.stream_ptr()), "dv_noise_prepare_f64")
-        return n01, n01f
+        return ddim.noise_prepare(self.time_embedding, x_t, t, shift)
 
     def _aggregate(self, volume, n01f):
         """pwcnet_ddim.py:472-477: (volume * filter) -> dres2 -> dres3 -> dres4 -> classif3."""
@@ -733,34 +681,9 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         return unc
 
     def _step_coef(self, time, time_next, cof):
-        p = self.prepare()
-        k = _lib.DvDdimCoef()
-        k.sqrt_recip_alpha, k.sqrt_recipm1_alpha = float(p.sqrt_recip[time]), float(p.sqrt_recipm1[time])
-        k.dif_thr, k.unc_thr, k.cof = self.dif_threshold, self.unc_threshold, cof
-        k.last = int(time_next < 0)
-        k.clamp_max, k.ens_dif_thr = float(self.maxdisp - 1), 0.0
-        if time_next >= 0:
-            alpha, alpha_next = p.alphas_cumprod[time], p.alphas_cumprod[time_next]
-            sigma = self.ddim_sampling_eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-            k.sigma, k.c = float(sigma), float((1 - alpha_next - sigma ** 2).sqrt())
-            k.sqrt_alpha_next = float(alpha_next.sqrt())
-        return k
-
-    def _ddim_update(self, disp, unc, used, n01, eps, fill, mask, ens, coef, want_pred_noise=False):
-        b, c, h, w = n01.shape
-        dev = disp.device
-        x_start = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
-        x_next = None if coef.last else torch.empty((b, c, h, w), dtype=torch.float64, device=dev)
-        pred_noise = torch.empty((b, c, h, w), dtype=torch.float64, device=dev) if want_pred_noise else None
-        f32 = n01.dtype == torch.float32
-        eps32 = eps if (eps is not None and eps.dtype == torch.float32) else None
-        eps64 = eps if (eps is not None and eps.dtype == torch.float64) else None
-        _lib.check(_lib.load().dv_ddim_step(disp.data_ptr(), unc.data_ptr(), used.data_ptr(), 0,
-                                            n01.data_ptr() if f32 else 0, 0 if f32 else n01.data_ptr(),
-                                            _lib.ptr(eps32), _lib.ptr(eps64), _lib.ptr(fill), mask.data_ptr(),
-                                            x_start.data_ptr(), _lib.ptr(pred_noise), _lib.ptr(x_next), _lib.ptr(ens),
-                                            b, c, h, w, ctypes.byref(coef), _lib.stream_ptr()), "dv_ddim_step")
-        return x_start, x_next, pred_noise
+        return ddim.step_coef(self.prepare().ddim, time, time_next, cof, eta=self.ddim_sampling_eta,
+                              dif_thr=self.dif_threshold, unc_thr=self.unc_threshold,
+                              clamp_max=float(self.maxdisp - 1), ens_dif_thr=0.0)
 
     def _predict(self, volume, img, t, features_left, features_right, shift=None, resized=None):
         n01, n01f = self._filter(img, t, shift)
@@ -780,34 +703,21 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
             n01, cost, disp, unc = self._predict(volume, noise, t, features_left, features_right)
             coef = self._step_coef(int(t.reshape(-1)[0]), -1, 0.0)
             mask = torch.zeros((b, h, w), dtype=torch.float32, device=volume.device)
-            x_start, _, pred_noise = self._ddim_update(disp, unc, disp, n01, None, None, mask, None, coef, True)
+            x_start, _, pred_noise = ddim.ddim_update(disp, disp, n01, None, None, mask, None, coef, unc=unc,
+                                                      want_pred_noise=True)
         return pred_noise, x_start, disp, ProbVolumeHandle(cost, unc, self.maxdisp, align_corners=True)
 
     @torch.no_grad()
-    def ddim_sample(self, volume, used, asd, features_left, features_right, noise: Optional[NoiseFn] = None,
+    def ddim_sample(self, volume, used, asd, features_left, features_right, noise: Optional[ddim.NoiseFn] = None,
                     generator: Optional[torch.Generator] = None, trace=None):
         """pwcnet_ddim.py:530-602.  Random draws in reference order: 'x_T' (torch.randn, :541), then per
         non-final step 'eps' (randn_like(img), :585) and 'q' (randn_like(asd) inside q_sample, :590)."""
         volume = _dev_f32(volume, "volume")
-        used = _dev_f32(used, "used")
+        used = ddim.check_loop_args(volume, _dev_f32(used, "used"), asd, self.maxdisp, what="fused volume")
         b, _, d, h, w = volume.shape
         dev = volume.device
-        if d != 48:
-            raise RuntimeError(f"the fused volume must have 48 disparity bins, got {d}")
-        if used.numel() != b * 16 * h * w or tuple(used.shape[-2:]) != (4 * h, 4 * w):
-            # the kernels index used / disp / ens as [B,4h,4w]; the reference fails at `disp - used` (:556)
-            raise RuntimeError(f"The size of tensor a {(b, 4 * h, 4 * w)} must match the size of tensor b "
-                               f"{tuple(used.shape)}: `used` must be the full-resolution disparity of the volume")
-        used = used.reshape(b, 4 * h, 4 * w)
-        if tuple(asd.shape) != (b, 48, h, w):
-            raise RuntimeError(f"x_T must be {(b, 48, h, w)}, got {tuple(asd.shape)}")
         p = self.prepare(check_weights=True)
-
-        def draw(kind, shape, dtype):
-            if noise is not None:
-                return noise(kind, shape, dtype).to(device=dev, dtype=dtype).contiguous()
-            return torch.randn(shape, device=dev, dtype=dtype, generator=generator)
-
+        draw = ddim.make_draw(noise, generator, dev)
         with torch.cuda.device(dev):
             img = draw("x_T", (b, 48, h, w), torch.float32)
             asd = asd.to(dev)
@@ -824,7 +734,7 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
                 if time_next >= 0:
                     eps = draw("eps", tuple(img.shape), img.dtype)
                     # asd = q_sample(asd, t): float64 from the first step on (float64 schedule buffers)
-                    asd = p.sqrt_ac[time].item() * asd.double() + p.sqrt_1mac[time].item() * draw("q", tuple(asd.shape), asd.dtype).double()
+                    asd = p.ddim.q_fill(time, asd, draw("q", tuple(asd.shape), asd.dtype))
                     fill = asd.contiguous()
                 if trace is not None:
                     trace(i, {"when": "in", "img": img, "mask": mask.clone(), "eps": eps, "fill": fill})
@@ -853,18 +763,12 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         st = self._loop_plan()[i]
         n01, cost, disp, unc = self._predict(volume, img, None, features_left, features_right,
                                              shift=st.shift_rows(volume.shape[0]), resized=resized)
-        x_start, x_next, _ = self._ddim_update(disp, unc, used, n01, eps, fill, mask, ens, st.coef)
+        x_start, x_next, _ = ddim.ddim_update(disp, used, n01, eps, fill, mask, ens, st.coef, unc=unc)
         return (disp, unc, x_start, x_next, cost) if want_cost else (disp, unc, x_start, x_next)
 
     @torch.no_grad()
     def encode_disparity(self, disp):
-        disp = _dev_f32(disp, "disp")
-        b, h, w = disp.shape[0], disp.shape[-2], disp.shape[-1]
-        x = torch.empty((b, 48, h, w), dtype=torch.float32, device=disp.device)
-        with torch.cuda.device(disp.device):
-            _lib.check(_lib.load().dv_encode_two_hot_f32(disp.data_ptr(), x.data_ptr(), b, 48, h * w,
-                                                         _lib.stream_ptr()), "dv_encode_two_hot_f32")
-        return x
+        return ddim.encode_two_hot(_dev_f32(disp, "disp"), 48)
 
     def train_forward(self, left, right, disp):
         """The reference's training branch (pwcnet_ddim.py:604-735) -> [pred0, combine, pred1, pred2, pred3,
