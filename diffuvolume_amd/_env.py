@@ -36,6 +36,10 @@ KNOBS = {
                         "torch = the group-wise-correlation and concatenation volumes in training as the PyTorch statements "
                         "of submodule.py (pad / unfold / flip, products, mean, cat) instead of the eval kernels with the "
                         "atomics-free HIP backward of csrc/volume_bwd.hip (A/B runs, tests)"),
+    "DV_TRAIN_REFINE": ("hip", "train_refine.route() on the refinement input of PWCNet_ddim training",
+                        "torch = left - warp(right, disp) and their +-24 correlation in training as the PyTorch statements "
+                        "(two F.grid_sample, a loop over 49 shifts; atomics in grid_sample's backward) instead of the fused "
+                        "HIP forward and the atomics-free HIP backward of csrc/warp_corr.hip (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

@@ -184,6 +184,11 @@ VOLUME_TRAIN_SIGNATURES = {
     "dv_concat_volume_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
     "dv_concat_volume_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
                                  held_by("test_gpu_volume_train.py::test_concat_abi_offset_views_bounds_and_refusals")),
+    "dv_warp_corr_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, P],
+                         held_by("test_gpu_refine_train.py::test_warp_corr_abi_offset_views_bounds_and_refusals")),
+    "dv_warp_corr_bwd_workspace_floats": (c_size_t, [I, I, I, I], SIZE_ONLY),
+    "dv_warp_corr_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+                             held_by("test_gpu_refine_train.py::test_warp_corr_abi_offset_views_bounds_and_refusals")),
 }
 
 

@@ -10,6 +10,7 @@
 // shifts of the first tile) is built in LDS, every output channel is written once, coalesced along W.  The
 // PyTorch composition makes ~110 launches and re-reads the feature maps once per shift.
 #include "dv_common.h"
+#include "warp_taps.h"   // Taps, make_taps, warp_one: shared with warp_corr.hip
 
 namespace {
 
@@ -25,51 +26,6 @@ struct RefArgs {
   float* out;           // [B,3C+1+49,H,W]
   int B, C, H, W;
 };
-
-// bilinear taps of grid_sample(align_corners=False, zeros padding) for output pixel (y, x) shifted by d
-struct Taps {
-  int x0, y0;           // north-west corner
-  float nw, ne, sw, se; // weights
-  float valid;          // 1 if the sampled all-ones image is >= 0.999, else 0
-};
-
-__device__ __forceinline__ Taps make_taps(float x, float y, float d, int W, int H) {
-  const float gx = 2.0f * (x - d) / (float)(W > 1 ? W - 1 : 1) - 1.0f;
-  const float gy = 2.0f * y / (float)(H > 1 ? H - 1 : 1) - 1.0f;
-  const float ix = ((gx + 1.f) * (float)W - 1.f) / 2.f;
-  const float iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  Taps t;
-  t.x0 = (int)fx; t.y0 = (int)fy;
-  t.nw = (fx + 1.f - ix) * (fy + 1.f - iy);
-  t.ne = (ix - fx) * (fy + 1.f - iy);
-  t.sw = (fx + 1.f - ix) * (iy - fy);
-  t.se = (ix - fx) * (iy - fy);
-  const bool xl = (unsigned)t.x0 < (unsigned)W, xr = (unsigned)(t.x0 + 1) < (unsigned)W;
-  const bool yt = (unsigned)t.y0 < (unsigned)H, yb = (unsigned)(t.y0 + 1) < (unsigned)H;
-  float m = 0.f;
-  if (xl && yt) m += t.nw;
-  if (xr && yt) m += t.ne;
-  if (xl && yb) m += t.sw;
-  if (xr && yb) m += t.se;
-  t.valid = m < 0.999f ? 0.f : 1.f;
-  if (!(xl && yt)) t.nw = 0.f;
-  if (!(xr && yt)) t.ne = 0.f;
-  if (!(xl && yb)) t.sw = 0.f;
-  if (!(xr && yb)) t.se = 0.f;
-  return t;
-}
-
-__device__ __forceinline__ float warp_one(const float* __restrict__ plane, const Taps& t, int W, int H) {
-  // out-of-range taps carry weight 0; clamp their addresses
-  const int xa = min(max(t.x0, 0), W - 1), xb = min(max(t.x0 + 1, 0), W - 1);
-  const int ya = min(max(t.y0, 0), H - 1), yb = min(max(t.y0 + 1, 0), H - 1);
-  float v = plane[(size_t)ya * W + xa] * t.nw;
-  v += plane[(size_t)ya * W + xb] * t.ne;
-  v += plane[(size_t)yb * W + xa] * t.sw;
-  v += plane[(size_t)yb * W + xb] * t.se;
-  return v * t.valid;
-}
 
 __global__ __launch_bounds__(256) void refine_inputs_kernel(RefArgs a) {
   __shared__ float frw_s[CMAX][SW];      // warped right features, columns x0-MD .. x0+TX+MD-1

@@ -33,6 +33,7 @@ from . import _lib, ddim, train2d, train3d
 from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
 from .head import DynamicHead
 from .train_tail import regress_head
+from .train_refine import warp_corr_train
 from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, refine_inputs,
@@ -820,9 +821,9 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
 
         # refinement (:711-728)
         rl, rr = self.refine_features(fl, fr, (hh, ww))
-        rr_warp = warp(rr, pred3)
-        corr = groupwise_corr_pm(rl, rr_warp, 24)
-        refine_in = torch.cat((rl - rr_warp, rl, self._dispupsample_train(pred3), pred3, corr), dim=1)
+        # left - warp(right, pred3) and their +-24 correlation with the HIP backward (train_refine.py; DV_TRAIN_REFINE)
+        diff, corr = warp_corr_train(rl, rr, pred3, 24)
+        refine_in = torch.cat((diff, rl, self._dispupsample_train(pred3), pred3, corr), dim=1)
         disp_finetune = self.refinenet3.train_forward(refine_in, pred3).squeeze(1)
         return [pred0, pred_combine, pred1, pred2, pred3.squeeze(1), disp_finetune]
 

@@ -1,5 +1,6 @@
 /* diffuvolume_hip_volume_train.h -- C ABI of libdiffuvolume_hip.so, third table: the backward of the two cost-volume
- * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h).
+ * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), and the warp +
+ * correlation of PWCNet_ddim's refinement input in training, forward and backward.
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -55,6 +56,34 @@ size_t dv_concat_volume_bwd_workspace_floats(int B, int C, int H, int W, int D);
 int dv_concat_volume_bwd_f32(const float* ref, const float* tgt, const float* s, const float* dvol, float* dref,
                              float* dtgt, float* ds, float* workspace, int B, int C, int H, int W, int D, int zero_left,
                              dv_stream_t stream);
+
+/* ---- warp + correlation of the refinement input, forward and backward ------------------------------------------------
+ * The part of PWCNet_ddim's refinement input that carries gradients (KITTI12/models/pwcnet_ddim.py:719-725):
+ *   F = warp(right, disp) (KITTI12/models/submodule.py:137-176: bilinear taps of grid_sample with align_corners=False on a
+ *   grid normalised by W-1 / H-1, times the validity m = [sampled ones >= 0.999]),
+ *   diff[B,C,H,W] = left - F,   corr[B,49,H,W] = build_corrleation_volume(left, F, 24, 1):
+ *   corr[i+24,x] = (1/C) sum_c left[c,x] F[c,x-i] for 0 <= i <= x;  corr[24-k,x] = (1/C) sum_c left[c,x] F[c,W-k+x] for
+ *   x < k (the reference's slices pair the first k columns of left with the LAST k columns of F), 0 elsewhere.
+ * diff and corr are channels [0,C) and [3C+1,3C+50) of dv_refine_inputs_f32 bit for bit.  disp is [B,H,W].
+ * C > 32, maxshift != 24 and W < 24: DV_ERR_UNSUPPORTED;  B or H above 65535: DV_ERR_SHAPE  (as dv_refine_inputs_f32). */
+int dv_warp_corr_f32(const float* left, const float* right, const float* disp, float* diff, float* corr, int B, int C,
+                     int H, int W, int maxshift, dv_stream_t stream);
+
+/* What autograd computes for those statements; F is recomputed, not saved.  With inv = 1/C and md = 24:
+ *   dleft[c,x]  = g_diff[c,x] + inv (sum_{0<=i<=md, i<=x} g_corr[i+md,x] F[c,x-i] + sum_{1<=k<=md, x<k} g_corr[md-k,x] F[c,W-k+x])
+ *   dF[c,x']    = -g_diff[c,x'] + inv (sum_{0<=i<=md, x'+i<W} g_corr[i+md,x'+i] left[c,x'+i]
+ *                                      + sum_{1<=k<=md, x'>=W-k} g_corr[md-k,x'-(W-k)] left[c,x'-(W-k)])
+ *   dright[c,ys,xs] = sum over the output pixels (y,x) and their in-range taps t on (ys,xs) of m(y,x) w_t(y,x) dF[c,y,x],
+ *                     in the order y ascending, x ascending
+ *   ddisp[y,x]  = -m W/max(W-1,1) sum_c dF[c,y,x] ((R[y0,x0+1] - R[y0,x0]) (fy+1-iy) + (R[y0+1,x0+1] - R[y0+1,x0]) (iy-fy)),
+ *                 R = right, taps outside the image count as 0; the validity carries no gradient.
+ * Each output may be NULL (not wanted); all three NULL: DV_ERR_NULL.  `workspace` holds m dF
+ * (dv_warp_corr_bwd_workspace_floats = B C H W floats); it is required (DV_ERR_NULL) when dright is wanted and may be NULL
+ * otherwise.  Refusals as dv_warp_corr_f32. */
+size_t dv_warp_corr_bwd_workspace_floats(int B, int C, int H, int W);
+int dv_warp_corr_bwd_f32(const float* left, const float* right, const float* disp, const float* g_diff, const float* g_corr,
+                         float* dleft, float* dright, float* ddisp, float* workspace, int B, int C, int H, int W,
+                         int maxshift, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
