@@ -40,6 +40,10 @@ KNOBS = {
                         "torch = left - warp(right, disp) and their +-24 correlation in training as the PyTorch statements "
                         "(two F.grid_sample, a loop over 49 shifts; atomics in grid_sample's backward) instead of the fused "
                         "HIP forward and the atomics-free HIP backward of csrc/warp_corr.hip (A/B runs, tests)"),
+    "DV_TRAIN_NORM": ("hip", "train_norm.route() on every BatchNorm3d of the ACVNet_DDIM / PWCNet_ddim 3-D stacks in training",
+                      "torch = BatchNorm3d with batch statistics, the hourglass skip add and the ReLU / Mish behind it in "
+                      "training as the PyTorch statements (F.batch_norm, the add, F.relu / x * tanh(softplus(x))) instead of the "
+                      "fused HIP forward and the atomics-free HIP backward of csrc/bn3d_act.hip (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

@@ -189,6 +189,13 @@ VOLUME_TRAIN_SIGNATURES = {
     "dv_warp_corr_bwd_workspace_floats": (c_size_t, [I, I, I, I], SIZE_ONLY),
     "dv_warp_corr_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
                              held_by("test_gpu_refine_train.py::test_warp_corr_abi_offset_views_bounds_and_refusals")),
+    "dv_bn3d_train_workspace_floats": (c_size_t, [I, I, I], SIZE_ONLY),
+    "dv_bn3d_stats_f32": (c_int, [P, P, P, P, P, P, I, I, I, c_float, c_float, P],
+                          held_by("test_gpu_norm_train.py::test_bn3d_abi_offset_views_bounds_and_refusals")),
+    "dv_bn3d_apply_act_f32": (c_int, [P, P, P, P, P, P, P, I, I, I, I, P],
+                              held_by("test_gpu_norm_train.py::test_bn3d_abi_offset_views_bounds_and_refusals")),
+    "dv_bn3d_act_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+                            held_by("test_gpu_norm_train.py::test_bn3d_abi_offset_views_bounds_and_refusals")),
 }
 
 

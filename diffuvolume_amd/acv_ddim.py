@@ -30,6 +30,7 @@ from . import _lib
 from . import ddim
 from . import train3d
 from .train_tail import regress_head
+from .train_norm import bn_act
 from . import train_volume
 from .train_volume import build_concat_volume_train
 from .head import DynamicHead
@@ -175,26 +176,29 @@ class Hourglass(nn.Module):
         c3 = _train_cbr(self.conv3[0], c2)
         c4 = _train_cbr(self.conv4[0], c3)
         c4 = _train_window_attention(self.attention_block, c4)
-        c5 = F.relu(self.conv5[1](train3d.conv_transpose3d_module(self.conv5[0], c4)) + _train_cb(self.redir2, c2),
-                    inplace=True)
-        return F.relu(self.conv6[1](train3d.conv_transpose3d_module(self.conv6[0], c5)) + _train_cb(self.redir1, x),
-                      inplace=True)
+        redir = _train_cb(self.redir2, c2)
+        c5 = bn_act(self.conv5[1], train3d.conv_transpose3d_module(self.conv5[0], c4), "relu", skip=redir)
+        redir = _train_cb(self.redir1, x)
+        return bn_act(self.conv6[1], train3d.conv_transpose3d_module(self.conv6[0], c5), "relu", skip=redir)
 
 
-def _train_cb(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    """convbn_3d in training: the convolution on the HIP route, BatchNorm3d (batch statistics) in PyTorch."""
-    return seq[1](train3d.conv3d_module(seq[0], x))
+def _train_cb(seq: nn.Sequential, x: torch.Tensor, act: str = "none") -> torch.Tensor:
+    """convbn_3d in training: the convolution on the HIP route, BatchNorm3d (batch statistics) and the activation behind
+    it on the route of `train_norm` (DV_TRAIN_NORM: the fused HIP kernels or the PyTorch statement)."""
+    return bn_act(seq[1], train3d.conv3d_module(seq[0], x), act)
 
 
 def _train_cbr(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    return F.relu(_train_cb(seq, x), inplace=True)
+    return _train_cb(seq, x, "relu")
 
 
 def _train_pair(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     """convbn-ReLU-conv[bn][-ReLU] stacks (dres0 / dres1 / classif*, acv_ddim.py:200-222) in training."""
     y = _train_cbr(seq[0], x)
     last = seq[2]
-    y = _train_cb(last, y) if isinstance(last, nn.Sequential) else train3d.conv3d_module(last, y)
+    if isinstance(last, nn.Sequential):
+        return _train_cb(last, y, "relu" if len(seq) > 3 else "none")
+    y = train3d.conv3d_module(last, y)
     return F.relu(y, inplace=True) if len(seq) > 3 else y
 
 

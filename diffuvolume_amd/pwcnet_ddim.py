@@ -16,9 +16,9 @@ concatenations.
 Differences from the ACV flavour: x_T = randn, 3 steps, fill = cumulative
 q_sample(asd), thresholds dif<1 & unc<1, ensemble [0.9,0,0,0.1], Mish activations.
 Training (``model.train()``, the reference's :643-735 branch): ``forward`` returns
-``[pred0, combine, pred1, pred2, pred3, disp_finetune]`` with the 3-D convolutions on ``train3d.py``, the 2-D
-convolutions of ``refinenet3`` on ``train2d.py`` and everything else (feature CNN, BatchNorm, Mish, warp,
-correlation, ``dispupsample`` in float64) on PyTorch autograd; on CPU tensors it raises.
+``[pred0, combine, pred1, pred2, pred3, disp_finetune]`` with the 3-D convolutions on ``train3d.py``, the BatchNorm3d +
+Mish behind them on ``train_norm.py``, the 2-D convolutions of ``refinenet3`` on ``train2d.py`` and the rest (feature
+CNN, BatchNorm2d and its Mish, ``dispupsample`` in float64) on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -34,6 +34,7 @@ from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
 from .head import DynamicHead
 from .train_tail import regress_head
 from .train_refine import warp_corr_train
+from .train_norm import bn_act
 from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, refine_inputs,
@@ -52,20 +53,39 @@ def fmish(x):
     return x * torch.tanh(F.softplus(x))
 
 
-def _train_seq(seq: nn.Module, x: torch.Tensor) -> torch.Tensor:
-    """A Sequential of the training graph: 3-D convolutions on `train3d`, 2-D ones on `train2d` (refinenet3 only),
-    BatchNorm and Mish in PyTorch."""
-    for m in (seq if isinstance(seq, nn.Sequential) else (seq,)):
+def _train_seq(seq: nn.Module, x: torch.Tensor, act: str = "none", skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A Sequential of the training graph, then `+ skip` and `act` ("none" / "mish"): 3-D convolutions on `train3d`, 2-D
+    ones on `train2d` (refinenet3 only).  A BatchNorm3d goes to `train_norm.bn_act` together with what follows it -- the
+    Mish behind it in the walk, or the caller's skip and activation when it ends the walk (the hourglass tails) -- so that
+    DV_TRAIN_NORM=hip runs them as one kernel; everything else (BatchNorm2d, a Mish behind something else) stays PyTorch."""
+    mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        last = i == len(mods) - 1
+        a, s, step = (act, skip, 1) if last else ("none", None, 1)
+        if not last and isinstance(mods[i + 1], Mish) and (i + 2 < len(mods) or (act == "none" and skip is None)):
+            a, s, step = "mish", None, 2                       # m and the Mish behind it as one statement
         if isinstance(m, nn.Sequential):
-            x = _train_seq(m, x)
-        elif isinstance(m, nn.ConvTranspose3d):
-            x = train3d.conv_transpose3d_module(m, x)
-        elif isinstance(m, nn.Conv3d):
-            x = train3d.conv3d_module(m, x)
-        elif isinstance(m, nn.Conv2d):
-            x = train2d.conv2d_module(m, x)
+            x = _train_seq(m, x, a, s)
+        elif isinstance(m, nn.BatchNorm3d):
+            x = bn_act(m, x, a, s)
         else:
-            x = m(x)
+            if isinstance(m, nn.ConvTranspose3d):
+                x = train3d.conv_transpose3d_module(m, x)
+            elif isinstance(m, nn.Conv3d):
+                x = train3d.conv3d_module(m, x)
+            elif isinstance(m, nn.Conv2d):
+                x = train2d.conv2d_module(m, x)
+            else:
+                x = m(x)
+            if s is not None:
+                x = x + s
+            if a == "mish":
+                x = fmish(x)
+            elif a != "none":
+                raise ValueError(f"act must be 'none' or 'mish', got {a!r}")
+        i += step
     return x
 
 
@@ -254,9 +274,9 @@ class HourglassUp(nn.Module):
         c2 = _train_seq(self.conv2, _train_seq(self.combine1, torch.cat((_train_seq(self.conv1, x), f4), dim=1)))
         c4 = _train_seq(self.conv4, _train_seq(self.combine2, torch.cat((_train_seq(self.conv3, c2), f5), dim=1)))
         c6 = _train_seq(self.conv6, _train_seq(self.combine3, torch.cat((_train_seq(self.conv5, c4), f6), dim=1)))
-        c7 = fmish(_train_seq(self.conv7, c6) + _train_seq(self.redir3, c4))
-        c8 = fmish(_train_seq(self.conv8, c7) + _train_seq(self.redir2, c2))
-        return fmish(_train_seq(self.conv9, c8) + _train_seq(self.redir1, x))
+        c7 = _train_seq(self.conv7, c6, "mish", skip=_train_seq(self.redir3, c4))
+        c8 = _train_seq(self.conv8, c7, "mish", skip=_train_seq(self.redir2, c2))
+        return _train_seq(self.conv9, c8, "mish", skip=_train_seq(self.redir1, x))
 
 
 class Hourglass(nn.Module):
@@ -279,8 +299,8 @@ class Hourglass(nn.Module):
         """Training path (pwcnet_ddim.py:235-248); eval runs ``_HourglassPlan``."""
         c2 = _train_seq(self.conv2, _train_seq(self.conv1, x))
         c4 = _train_seq(self.conv4, _train_seq(self.conv3, c2))
-        c5 = fmish(_train_seq(self.conv5, c4) + _train_seq(self.redir2, c2))
-        return fmish(_train_seq(self.conv6, c5) + _train_seq(self.redir1, x))
+        c5 = _train_seq(self.conv5, c4, "mish", skip=_train_seq(self.redir2, c2))
+        return _train_seq(self.conv6, c5, "mish", skip=_train_seq(self.redir1, x))
 
 
 # ---- prepared hot-path layers ---------------------------------------------------------------------

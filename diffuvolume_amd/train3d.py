@@ -13,7 +13,7 @@
 ``conv_transpose3d_k4(x, w)`` (k4 s2 p1, bias-free: the IGEV hourglass's conv3_up / conv2_up / conv1_up) has kernels of
 its own for both gradients (csrc/deconv3d_k4_bwd.hip); ``feature_gate_train(cv, logit)`` is FeatureAtt's
 ``sigmoid(logit) * cv`` with ``dv_feature_gate_bwd_f32`` as its backward.
-BatchNorm and ReLU stay PyTorch.  ``DV_TRAIN_CONV3D=torch`` routes every function to its torch expression (``F.conv3d``,
+BatchNorm3d and the activation behind it are ``train_norm.py``'s.  ``DV_TRAIN_CONV3D=torch`` routes every function to its torch expression (``F.conv3d``,
 ``F.conv_transpose3d``, ``torch.sigmoid(logit).unsqueeze(2) * cv``) instead (A/B runs, tests).  CPU tensors raise, as
 everywhere on the hot path."""
 from __future__ import annotations

@@ -1,6 +1,7 @@
 /* diffuvolume_hip_volume_train.h -- C ABI of libdiffuvolume_hip.so, third table: the backward of the two cost-volume
- * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), and the warp +
- * correlation of PWCNet_ddim's refinement input in training, forward and backward.
+ * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), the warp +
+ * correlation of PWCNet_ddim's refinement input in training, forward and backward, and the BatchNorm3d (batch statistics)
+ * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward.
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -84,6 +85,47 @@ size_t dv_warp_corr_bwd_workspace_floats(int B, int C, int H, int W);
 int dv_warp_corr_bwd_f32(const float* left, const float* right, const float* disp, const float* g_diff, const float* g_corr,
                          float* dleft, float* dright, float* ddisp, float* workspace, int B, int C, int H, int W,
                          int maxshift, dv_stream_t stream);
+
+/* ---- BatchNorm3d with batch statistics + skip + activation, forward and backward --------------------------------------
+ * What nn.BatchNorm3d computes in training mode, the optional add of a second tensor and the activation behind it, as the
+ * 3-D stacks of ACVNet_DDIM (ReLU) and PWCNet_ddim (Mish) apply them to a convolution's output:
+ *   x, skip, y [B,C,S] with S = D*H*W;  mean, invstd, gamma, beta, running_mean, running_var [C];  n = B*S
+ *   mean[c] = (1/n) sum_{b,s} x[b,c,s],  var[c] = (1/n) sum (x - mean)^2,  invstd = 1 / sqrt(var + eps)
+ *   y = act((x - mean) * invstd * gamma + beta + skip),  act in {DV_ACT_NONE, DV_ACT_RELU, DV_ACT_MISH}
+ * Every kernel gives one block one chunk of 8192 consecutive floats of one (b,c) slab.  Reductions are one partial per block
+ * in `workspace`, then a combine launch of one wave per channel that merges a channel's partials in a fixed order in
+ * double: no atomics, the same bits on every launch.  Here, unlike the builders above, the 16-byte path (S % 4 == 0 and
+ * every tensor operand on a 16-byte line) and the scalar path assign the same elements to the same thread in the same
+ * order, so they agree in bits.
+ *
+ * dv_bn3d_train_workspace_floats: floats of `workspace` for both launching entries below, C * (3 P + 2) with
+ *   P = B * ceil(S / 8192) partials per channel; 0 for a non-positive size.
+ *
+ * dv_bn3d_stats_f32: partials (count, mean, M2) in the shifted form (sums of x - K and (x - K)^2 with K the chunk's first
+ *   element, in fp32), merged with Chan's formula.  Writes mean and invstd.  running_mean / running_var: both or neither
+ *   (DV_ERR_NULL otherwise); when given they are updated in place, r = (1 - momentum) r + momentum * (mean | var n/(n-1)).
+ *   B*S == 1: DV_ERR_UNSUPPORTED (no variance; PyTorch raises there too).  eps < 0: DV_ERR_SHAPE.
+ *
+ * dv_bn3d_apply_act_f32: y from x, the statistics and the affine parameters; skip may be NULL.
+ *   act outside the three above: DV_ERR_UNSUPPORTED.
+ *
+ * dv_bn3d_act_bwd_f32: with z recomputed by the forward's statement and xhat = (x - mean) invstd,
+ *   dz = dy act'(z);  ReLU' = [z > 0];  Mish' = t + z (1 - t^2) e / (1 + e) with e = exp(z), n = e (e + 2), t = n / (n + 2)
+ *   (dv_act's e and n), 1 for z > 20
+ *   dskip = dz,  dbeta[c] = sum dz,  dgamma[c] = sum dz xhat,
+ *   dx = gamma invstd (dz - dbeta / n - xhat dgamma / n)
+ *   Pass 1 writes dz (into dskip when that is wanted, otherwise into dx as scratch; not at all when act is DV_ACT_NONE and
+ *   skip is NULL, where dz is dy) and the per-block sums; the combine gives dbeta and dgamma; pass 2 forms dx in place.
+ *   dx, dskip, dgamma, dbeta may each be NULL (not wanted: dx == NULL saves pass 2); all four NULL: DV_ERR_NULL.
+ *   dskip without skip: DV_ERR_NULL.  dx must not overlap dy, x or skip.  Refusals as above. */
+size_t dv_bn3d_train_workspace_floats(int B, int C, int S);
+int dv_bn3d_stats_f32(const float* x, float* mean, float* invstd, float* running_mean, float* running_var,
+                      float* workspace, int B, int C, int S, float momentum, float eps, dv_stream_t stream);
+int dv_bn3d_apply_act_f32(const float* x, const float* skip, const float* mean, const float* invstd, const float* gamma,
+                          const float* beta, float* y, int B, int C, int S, int act, dv_stream_t stream);
+int dv_bn3d_act_bwd_f32(const float* dy, const float* x, const float* skip, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, float* dx, float* dskip, float* dgamma, float* dbeta,
+                        float* workspace, int B, int C, int S, int act, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
