@@ -44,6 +44,11 @@ KNOBS = {
                       "torch = BatchNorm3d with batch statistics, the hourglass skip add and the ReLU / Mish behind it in "
                       "training as the PyTorch statements (F.batch_norm, the add, F.relu / x * tanh(softplus(x))) instead of the "
                       "fused HIP forward and the atomics-free HIP backward of csrc/bn3d_act.hip (A/B runs, tests)"),
+    "DV_TRAIN_PATCH": ("hip", "train_patch.route() on the patch stencils of ACVNet_DDIM's attention branch in training",
+                       "torch = the four depth-wise (1,3,3) convolutions behind the group-wise correlation volume (patch, "
+                       "patch_l1..3) in training as the nn.Conv3d calls, slices and torch.cat (MIOpen's grouped convolutions "
+                       "forward and backward) instead of the fused HIP forward of csrc/patch_volume.hip and the atomics-free "
+                       "HIP backward of csrc/patch_volume_bwd.hip (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

@@ -196,6 +196,9 @@ VOLUME_TRAIN_SIGNATURES = {
                               held_by("test_gpu_norm_train.py::test_bn3d_abi_offset_views_bounds_and_refusals")),
     "dv_bn3d_act_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
                             held_by("test_gpu_norm_train.py::test_bn3d_abi_offset_views_bounds_and_refusals")),
+    "dv_patch_volume_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
+    "dv_patch_volume_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
+                                held_by("test_gpu_patch_train.py::test_patch_bwd_abi_offset_views_bounds_and_refusals")),
 }
 
 

@@ -15,7 +15,7 @@ The dead pre-DDIM aggregation pass of the reference's eval branch (acv_ddim.py:3
 its result ``pred2`` is never returned) is skipped; outputs are unchanged.
 Training (``model.train()``, the reference's :424-482 branch): ``forward`` returns
 ``[pred_attention, pred0, pred1, pred2]`` with the 3-D convolutions on the differentiable HIP route of
-``train3d.py`` and everything else on PyTorch autograd; on CPU tensors it raises.
+``train3d.py``, the patch stencils on ``train_patch.py`` and everything else on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -33,11 +33,16 @@ from .train_tail import regress_head
 from .train_norm import bn_act
 from . import train_volume
 from .train_volume import build_concat_volume_train
+from . import train_patch
+from .train_patch import patch_volume_train
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
                         AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
                         check_split_overflow, default_conv_precision, patch_volume, upsample_softmax_regress, window_attention)
+
+
+PATCH_DILATION = (1,) * 8 + (2,) * 16 + (3,) * 16      # patch_l1 / patch_l2 / patch_l3 on groups 0-7 / 8-23 / 24-39
 
 
 def any_split_plan(plans) -> bool:
@@ -572,8 +577,14 @@ class ACVNet_DDIM(_HipPlanMixin):
         fl = self.feature_extraction(left)["gwc_feature"]
         fr = self.feature_extraction(right)["gwc_feature"]
         gwc = build_gwc_volume(fl, fr, self.maxdisp // 4, self.num_groups)
-        gwc = self.patch(gwc)
-        patch = torch.cat((self.patch_l1(gwc[:, :8]), self.patch_l2(gwc[:, 8:24]), self.patch_l3(gwc[:, 24:40])), dim=1)
+        if train_patch.route() == "hip":
+            # :377-381 as one fused pass forward and one backward; autograd splits the gradient onto the four weights
+            patch = patch_volume_train(gwc, self.patch.weight.reshape(40, 9),
+                                       torch.cat([m.weight.reshape(-1, 9) for m in (self.patch_l1, self.patch_l2, self.patch_l3)]),
+                                       PATCH_DILATION)
+        else:
+            gwc = self.patch(gwc)
+            patch = torch.cat((self.patch_l1(gwc[:, :8]), self.patch_l2(gwc[:, 8:24]), self.patch_l3(gwc[:, 24:40])), dim=1)
         cost_attention = _train_pair(self.dres1_att_, patch)
         cost_attention = self.dres2_att_(cost_attention)
         att_weights = _train_pair(self.classif_att_, cost_attention)

@@ -1,7 +1,8 @@
 /* diffuvolume_hip_volume_train.h -- C ABI of libdiffuvolume_hip.so, third table: the backward of the two cost-volume
  * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), the warp +
- * correlation of PWCNet_ddim's refinement input in training, forward and backward, and the BatchNorm3d (batch statistics)
- * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward.
+ * correlation of PWCNet_ddim's refinement input in training, forward and backward, the BatchNorm3d (batch statistics)
+ * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, and the backward of the
+ * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32).
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -126,6 +127,33 @@ int dv_bn3d_apply_act_f32(const float* x, const float* skip, const float* mean, 
 int dv_bn3d_act_bwd_f32(const float* dy, const float* x, const float* skip, const float* mean, const float* invstd,
                         const float* gamma, const float* beta, float* dx, float* dskip, float* dgamma, float* dbeta,
                         float* workspace, int B, int C, int S, int act, dv_stream_t stream);
+
+/* ---- patch stencils of the attention branch, backward ------------------------------------------------------------------
+ * What autograd computes for the four depth-wise Conv3d(.., (1,3,3), groups) the attention branch applies to the group-wise
+ * correlation volume (SceneFlow/models/acv_ddim.py:181-188 define them, :377-381 apply them):
+ *   gwc = patch(gwc);  out = cat(patch_l1(gwc[:, :8]), patch_l2(gwc[:, 8:24]), patch_l3(gwc[:, 24:40]))   dilation 1 / 2 / 3
+ * i.e. for the forward dv_patch_volume_runs_f32 (diffuvolume_hip.h), which stays as it is.  Per plane (b, g, d) with dl the
+ * dilation of group g, (k-1) the 2-D tap offset (ky-1, kx-1), x = gwc, go = dout:
+ *   gwc, dout, dgwc [B,G,D,H,W];  w1, w2, dw1, dw2 [G,9]
+ *   mid[p]  = sum_k w1[k] x[p + (k-1)]          for p in the image, 0 outside (recomputed on chip, never stored)
+ *   dmid[p] = sum_k w2[k] go[p - (k-1) dl]      for p in the image, 0 outside;  go = 0 outside
+ *   dgwc[p] = sum_k w1[k] dmid[p - (k-1)]
+ *   dw2[g,k] = sum_{b,d,p} go[p] mid[p + (k-1) dl],   dw1[g,k] = sum_{b,d,p} dmid[p] x[p + (k-1)]
+ * One pass over 16 x 128 tiles reads gwc and dout once and writes dgwc once.  Each block leaves its 18 partial sums in the
+ * `workspace` slot of its block index; a second launch adds a group's slots in a fixed order in double.  The groups are
+ * given as HOST-side runs of consecutive groups with one dilation (as to dv_patch_volume_runs_f32): one launch per run and
+ * per 65535 planes.  16-byte accesses when W % 4 == 0 and gwc, dout and dgwc lie on 16-byte lines, element-wise accesses
+ * otherwise; here the two paths do the same arithmetic in the same order and agree in bits.
+ *
+ * dgwc, dw1, dw2 may each be NULL (not wanted; that work is skipped: without dw1 and dw2 gwc is not read), and a result
+ * has the same bits whichever of the others are wanted; all three NULL: DV_ERR_NULL.  `workspace`
+ * (dv_patch_volume_bwd_workspace_floats = G * B*D*ceil(H/16)*ceil(W/128) * 18 floats; 0 for a non-positive size) is
+ * required (DV_ERR_NULL) when dw1 or dw2 is wanted and may be NULL otherwise.  dgwc must not overlap gwc or dout.
+ * Non-positive sizes, runs that do not tile 0..G in order, a dilation outside 1..3: DV_ERR_SHAPE. */
+size_t dv_patch_volume_bwd_workspace_floats(int B, int G, int D, int H, int W);
+int dv_patch_volume_bwd_f32(const float* gwc, const float* w1, const float* w2, const float* dout, float* dgwc, float* dw1,
+                            float* dw2, float* workspace, int B, int G, int D, int H, int W, int nruns, const int* run_g0,
+                            const int* run_ng, const int* run_dil, dv_stream_t stream);
 
 #ifdef __cplusplus
 }

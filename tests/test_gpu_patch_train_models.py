@@ -1,0 +1,89 @@
+"""ACVNet_DDIM training steps with the patch stencils of the attention branch on the fused HIP kernels (DV_TRAIN_PATCH=hip)
+and on the nn.Conv3d calls (DV_TRAIN_PATCH=torch), on the recorded step of test_gpu_acv_train.py (its `fresh_model`, `step`
+and checks are used as they are).  PWCNet_ddim has no patch stencils.
+
+The module runs one step per route, once, and the tests below read those."""
+import gc
+
+import numpy as np
+import pytest
+import torch
+
+import test_gpu_acv_train as acv_t
+from diffuvolume_amd import patch_volume_train
+from diffuvolume_amd.acv_ddim import PATCH_DILATION
+
+pytestmark = pytest.mark.gpu
+
+FN = "PatchVolumeFnBackward"
+PATCH = ("patch.weight", "patch_l1.weight", "patch_l2.weight", "patch_l3.weight")
+
+
+def in_graph(fn, name):
+    seen, stack = set(), [fn]
+    while stack:
+        f = stack.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        if f.name() == name:
+            return True
+        stack.extend(g for g, _ in f.next_functions)
+    return False
+
+
+def one_step(gold, route):
+    gc.collect()
+    torch.cuda.empty_cache()
+    model = acv_t.fresh_model(gold)
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("DV_TRAIN_PATCH", route)
+        outs, loss = acv_t.step(model, gold, mp)
+    return dict(model=model, outs=[o.detach() for o in outs], loss=loss.detach(), found=in_graph(outs[0].grad_fn, FN))
+
+
+@pytest.fixture(scope="module")
+def steps():
+    from conftest import GOLDEN
+    with np.load(GOLDEN / "acv_train_step.npz") as z:
+        gold = {k: z[k] for k in z.files}
+    return gold, {"hip": one_step(gold, "hip"), "torch": one_step(gold, "torch")}
+
+
+def test_the_function_is_in_the_graph_on_hip_and_not_on_torch(steps):
+    _, runs = steps
+    assert runs["hip"]["found"] and not runs["torch"]["found"]
+    for r in runs.values():
+        grads = dict(r["model"].named_parameters())
+        assert all(grads[n].grad is not None and bool((grads[n].grad != 0).any()) for n in PATCH)
+    assert list(runs["hip"]["model"].state_dict()) == list(runs["torch"]["model"].state_dict())
+
+
+@pytest.mark.parametrize("route", ["hip", "torch"])
+def test_recorded_training_step_on_both_routes(steps, route):
+    gold, runs = steps
+    r = runs[route]
+    acv_t.test_step_matches_reference(gold, (r["model"], r["outs"], r["loss"]))
+
+
+def test_the_same_volume_twice_gives_the_patch_gradients_bit_for_bit(steps, monkeypatch):
+    """The call site's expression on the model's own parameters, fed one gwc volume and one cotangent twice."""
+    monkeypatch.setenv("DV_TRAIN_PATCH", "hip")
+    gold, runs = steps
+    model = runs["hip"]["model"]
+    b, h, w = (int(v) for v in gold["shape"])
+    gen = torch.Generator().manual_seed(41)
+    gwc = torch.randn(b, 40, 48, h // 4, w // 4, generator=gen).cuda()
+    g = torch.randn(gwc.shape, generator=gen).cuda()
+    params = [dict(model.named_parameters())[n] for n in PATCH]
+    got = []
+    for _ in range(2):
+        x = gwc.clone().requires_grad_(True)
+        out = patch_volume_train(x, model.patch.weight.reshape(40, 9),
+                                 torch.cat([m.weight.reshape(-1, 9) for m in (model.patch_l1, model.patch_l2, model.patch_l3)]),
+                                 PATCH_DILATION)
+        assert out.grad_fn.name() == FN
+        got.append(torch.autograd.grad(out, [x] + params, g))
+    assert [tuple(t.shape) for t in got[0][1:]] == [tuple(p.shape) for p in params]
+    assert all(bool((t != 0).any()) for t in got[0])
+    assert all(torch.equal(p, q) for p, q in zip(*got))
