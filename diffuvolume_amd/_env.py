@@ -49,6 +49,11 @@ KNOBS = {
                        "patch_l1..3) in training as the nn.Conv3d calls, slices and torch.cat (MIOpen's grouped convolutions "
                        "forward and backward) instead of the fused HIP forward of csrc/patch_volume.hip and the atomics-free "
                        "HIP backward of csrc/patch_volume_bwd.hip (A/B runs, tests)"),
+    "DV_TRAIN_ATTN": ("hip", "train_attn.route() on the bottleneck window attention of ACVNet_DDIM's hourglasses in training",
+                      "torch = attention_block.forward in training as the PyTorch statements (pad, permute copies, F.linear, two "
+                      "batched matmuls, a softmax over a materialised [B, windows, 16, 64, 64] tensor, the 1x1x1 convolution) "
+                      "instead of the fused HIP forward of csrc/window_attn.hip and the atomics-free HIP backward of "
+                      "csrc/window_attn_bwd.hip (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

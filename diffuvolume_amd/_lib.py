@@ -199,6 +199,9 @@ VOLUME_TRAIN_SIGNATURES = {
     "dv_patch_volume_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
     "dv_patch_volume_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
                                 held_by("test_gpu_patch_train.py::test_patch_bwd_abi_offset_views_bounds_and_refusals")),
+    "dv_window_attn3d_bwd_workspace_floats": (c_size_t, [I, I, I, I, I, I], SIZE_ONLY),
+    "dv_window_attn3d_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+                                 held_by("test_gpu_attn_train.py::test_attn_bwd_abi_offset_views_bounds_and_refusals")),
 }
 
 

@@ -15,7 +15,8 @@ The dead pre-DDIM aggregation pass of the reference's eval branch (acv_ddim.py:3
 its result ``pred2`` is never returned) is skipped; outputs are unchanged.
 Training (``model.train()``, the reference's :424-482 branch): ``forward`` returns
 ``[pred_attention, pred0, pred1, pred2]`` with the 3-D convolutions on the differentiable HIP route of
-``train3d.py``, the patch stencils on ``train_patch.py`` and everything else on PyTorch autograd; on CPU tensors it raises.
+``train3d.py``, the patch stencils on ``train_patch.py``, the hourglasses' window attention on ``train_attn.py`` and
+everything else on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ from . import train_volume
 from .train_volume import build_concat_volume_train
 from . import train_patch
 from .train_patch import patch_volume_train
+from .train_attn import window_attention_train
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
@@ -207,36 +209,10 @@ def _train_pair(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     return F.relu(y, inplace=True) if len(seq) > 3 else y
 
 
-def _train_window_attention(ab: "_WindowAttention", x: torch.Tensor, block: int = 4) -> torch.Tensor:
-    """attention_block.forward (SceneFlow/models/submodule.py:398-429) as differentiable PyTorch: multi-head
-    self-attention inside 4 x 4 x 4 windows, H and W zero-padded up to whole windows.  The reference's padding mask
-    (-1000 between a padded and an unpadded token) only takes effect when H AND W are both padded: with one of
-    them whole, its ``mask[:, -0:]`` slice marks every token (the eval kernel, csrc/window_attn.hip, does the same)."""
-    b, c, d, h0, w0 = x.shape
-    ph, pw = (-h0) % block, (-w0) % block
-    xp = F.pad(x, (0, pw, 0, ph))
-    h, w = h0 + ph, w0 + pw
-    nd, nh, nw = d // block, h // block, w // block
-    nwin, ntok, heads = nd * nh * nw, block ** 3, ab.num_heads
-    ch = c // heads
-    # tokens of one window contiguous: [B, windows, tokens, C], token = (z, y, x) inside the window
-    tok = xp.reshape(b, c, nd, block, nh, block, nw, block).permute(0, 2, 4, 6, 3, 5, 7, 1).reshape(b, nwin, ntok, c)
-    qkv = F.linear(tok, ab.qkv_3d.weight, ab.qkv_3d.bias).reshape(b, nwin, ntok, 3, heads, ch)
-    q, k, v = qkv.permute(3, 0, 1, 4, 2, 5).unbind(0)                  # [B, windows, heads, tokens, ch]
-    logits = (q @ k.transpose(-2, -1)) * ch ** -0.5
-    if ph and pw:
-        rows = torch.arange(h, device=x.device).view(nh, 1, block, 1) >= h0
-        cols = torch.arange(w, device=x.device).view(1, nw, 1, block) >= w0
-        padded = (rows | cols).reshape(nh * nw, 1, block * block)    # [h*w windows, 1, in-plane]
-        padded = padded.expand(nh * nw, block, block * block).reshape(nh * nw, ntok)      # depth repeats the plane
-        padded = padded.repeat(nd, 1)                                                      # [windows, tokens]
-        bias = torch.zeros((nwin, ntok, ntok), dtype=logits.dtype, device=x.device)
-        bias = bias.masked_fill(padded.unsqueeze(2) != padded.unsqueeze(1), -1000.0)
-        logits = logits + bias.unsqueeze(1)
-    y = torch.softmax(logits, dim=-1) @ v                               # [B, windows, heads, tokens, ch]
-    y = y.reshape(b, nd, nh, nw, heads, block, block, block, ch).permute(0, 4, 8, 1, 5, 2, 6, 3, 7)
-    y = y.reshape(b, c, d, h, w)[:, :, :, :h0, :w0]
-    return train3d.conv3d_module(ab.final1x1, y)
+def _train_window_attention(ab: "_WindowAttention", x: torch.Tensor) -> torch.Tensor:
+    """attention_block.forward (SceneFlow/models/submodule.py:398-429) in training on the route of `train_attn`
+    (DV_TRAIN_ATTN: the fused HIP forward and backward, or the PyTorch statement)."""
+    return window_attention_train(x, ab.qkv_3d.weight, ab.qkv_3d.bias, ab.final1x1.weight, ab.final1x1.bias, ab.num_heads)
 
 
 # --------------------------------------------------------------------------------------

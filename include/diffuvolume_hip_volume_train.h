@@ -1,8 +1,9 @@
 /* diffuvolume_hip_volume_train.h -- C ABI of libdiffuvolume_hip.so, third table: the backward of the two cost-volume
  * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), the warp +
  * correlation of PWCNet_ddim's refinement input in training, forward and backward, the BatchNorm3d (batch statistics)
- * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, and the backward of the
- * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32).
+ * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, the backward of the
+ * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32), and the backward of the hourglass's
+ * bottleneck window attention (dv_window_attn3d_f32).
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -154,6 +155,38 @@ size_t dv_patch_volume_bwd_workspace_floats(int B, int G, int D, int H, int W);
 int dv_patch_volume_bwd_f32(const float* gwc, const float* w1, const float* w2, const float* dout, float* dgwc, float* dw1,
                             float* dw2, float* workspace, int B, int G, int D, int H, int W, int nruns, const int* run_g0,
                             const int* run_ng, const int* run_dil, dv_stream_t stream);
+
+/* ---- 4x4x4 window attention of the hourglass bottleneck, backward ---------------------------------------------------------
+ * What autograd computes for attention_block.forward (SceneFlow/models/submodule.py:398-429), which the hourglass
+ * (SceneFlow/models/acv_ddim.py:56-93) applies at its bottleneck, i.e. for the forward dv_window_attn3d_f32
+ * (diffuvolume_hip.h), which stays as it is.  C = 128, heads = 16, head dim 8; D % 4 == 0; H and W are zero-padded up to
+ * whole windows.  Per window, X [64,128] the tokens (0 at padded tokens), dY [64,128] the gradient of the output (0 at
+ * padded tokens: the forward crops them), per head with its slices Q, K, V of QKV = X Wqkv^T + bqkv:
+ *   S = 8^-0.5 Q K^T (-1000 between a padded and an unpadded token when H AND W are padded),  P = softmax(S),  O = P V,
+ *   Y = Om Wp^T + bp with Om the heads of O side by side
+ *   dOm = dY Wp,  Dq = rowsum(dO * O),  dV = P^T dO,  dP = dO V^T,  dS = P * (dP - Dq),  dQ = 8^-0.5 dS K,  dK = 8^-0.5 dS^T Q
+ *   dx = dQKV Wqkv at unpadded tokens;  dqkv_w [384,128] = sum over tokens dQKV^T X;  dqkv_b [384] = sum over ALL tokens of
+ *   dQKV (padded tokens are keys and values with qkv = bias, so their dK and dV rows count);  dproj_w [128,128] = sum dY^T Om;
+ *   dproj_b [128] = sum dY.
+ * x, dout, dx [B,128,D,H,W]; qkv_w [384,128], qkv_b [384], proj_w [128,128] and their gradients in the same shapes.
+ * P is recomputed with the forward's arithmetic.  One block per window writes dx and, channel-major, Om and dQKV into
+ * `workspace`; the two weight gradients are then split-K GEMMs over the tokens (partials summed in split order); dqkv_b adds
+ * one partial per window and dproj_b the elements of dout in a fixed order in double.  No atomics: the same bits on every
+ * launch, and dx of a batch has the bits of its items run one by one.  16-byte stores to dx (to the workspace) when
+ * W % 4 == 0 and dx (the workspace) lies on a 16-byte line, element stores otherwise, with the same bits; x and dout need
+ * 4-byte alignment only.
+ *
+ * dx, dqkv_w, dqkv_b, dproj_w, dproj_b may each be NULL (not wanted; that work is skipped), and a result has the same bits
+ * whichever of the others are wanted; all five NULL: DV_ERR_NULL.  `workspace`
+ * (dv_window_attn3d_bwd_workspace_floats = 512 B D H W + 384 windows + min(T, 64) 384*128 + min(T, 128) 128*128 with
+ * T = B ceil(D H W / 32) chunks of tokens; 0 for invalid or unsupported arguments) is required (DV_ERR_NULL) when dqkv_w, dqkv_b or
+ * dproj_w is wanted and may be NULL otherwise.  dx and the workspace must not overlap x or dout.
+ * Refusals, before the device is touched, as dv_window_attn3d_f32: NULL inputs DV_ERR_NULL; non-positive sizes or
+ * D % 4 != 0 DV_ERR_SHAPE; C != 128 or heads != 16 DV_ERR_UNSUPPORTED; qkv_w or proj_w off a 16-byte line DV_ERR_ALIGN. */
+size_t dv_window_attn3d_bwd_workspace_floats(int B, int C, int D, int H, int W, int heads);
+int dv_window_attn3d_bwd_f32(const float* x, const float* qkv_w, const float* qkv_b, const float* proj_w, const float* dout,
+                             float* dx, float* dqkv_w, float* dqkv_b, float* dproj_w, float* dproj_b, float* workspace,
+                             int B, int C, int D, int H, int W, int heads, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
