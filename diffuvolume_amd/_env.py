@@ -3,7 +3,8 @@
 Nothing here changes results silently on the default path: every switch is either an opt-in alternative that gives the same
 bits (side stream, hipGraph replay), a documented numerics alternative (`DV_CONV_PRECISION`), or plumbing.  `overrides()`
 returns the ones that are set; bench.py prints that dict in its JSON line as `env_overrides`, so a measured number carries
-the switches it was measured under.  The native library reads NO environment variable (tests pin kernel choices through
+the switches it was measured under.  `route(knob)` is the one implementation of the ``DV_TRAIN_*`` route switches: no
+other module of the package reads one of them from the environment.  The native library reads NO environment variable (tests pin kernel choices through
 `dv_*_set_*` hooks of the C ABI)."""
 from __future__ import annotations
 
@@ -63,6 +64,17 @@ KNOBS = {
     "DV_BENCH_SELF_LAUNCHED": ("unset", "bench.py (set by bench.py for the ranks it starts itself)", "internal marker"),
     "DV_FULL_PARITY": ("unset", "tests/", "1 = the long parity runs (all steps against float64, second pair, diagnostic networks)"),
 }
+
+
+def route(knob: str) -> str:
+    """'hip' or 'torch': what the training route switch ``knob`` (a ``DV_TRAIN_*`` row of `KNOBS`) says now.  Read from
+    the environment on every call; unset or empty is the row's default.  Every ``train_*.route`` is this function bound
+    to its knob."""
+    default = KNOBS[knob][0]
+    r = os.environ.get(knob, default) or default
+    if r not in ("hip", "torch"):
+        raise ValueError(f"{knob} must be 'hip' or 'torch', got {r!r}")
+    return r
 
 
 def overrides() -> dict:

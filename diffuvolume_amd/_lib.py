@@ -5,6 +5,10 @@ There is deliberately no CPU / eager fallback: if the library is missing or a
 kernel reports an error the call raises.  ``import torch`` happens first so the
 library resolves libamdhip64 against the HIP runtime PyTorch already loaded
 (one runtime, one set of streams).
+
+What every training route needs around an entry is here once: ``check_f32`` (a float32 tensor on the GPU),
+``launch(name, device, *args)`` (the call on PyTorch's current stream of that device, its code checked) and
+``workspace(name, device, *dims)`` (the float32 scratch a ``*_workspace_floats`` entry sizes; None for 0).
 """
 from __future__ import annotations
 
@@ -245,3 +249,25 @@ def stream_ptr() -> int:
 
 def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
+
+
+def check_f32(t, name: str) -> None:
+    """The training routes' tensor check: a float32 tensor on the GPU, or an error that names it."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+
+
+def launch(name: str, device, *args) -> None:
+    """Call the entry ``name`` with ``args`` and PyTorch's current stream of ``device``; raise on its error code."""
+    with torch.cuda.device(device):
+        check(getattr(load(), name)(*args, stream_ptr()), name)
+
+
+def workspace(name: str, device, *dims):
+    """A float32 tensor on ``device`` of as many elements as the size entry ``name`` returns for ``dims``; None for 0."""
+    n = getattr(load(), name)(*dims)
+    return torch.empty(n, dtype=torch.float32, device=device) if n else None

@@ -34,7 +34,6 @@ from .train_tail import regress_head
 from .train_norm import bn_act
 from . import train_volume
 from .train_volume import build_concat_volume_train
-from . import train_patch
 from .train_patch import patch_volume_train
 from .train_attn import window_attention_train
 from .head import DynamicHead
@@ -553,14 +552,11 @@ class ACVNet_DDIM(_HipPlanMixin):
         fl = self.feature_extraction(left)["gwc_feature"]
         fr = self.feature_extraction(right)["gwc_feature"]
         gwc = build_gwc_volume(fl, fr, self.maxdisp // 4, self.num_groups)
-        if train_patch.route() == "hip":
-            # :377-381 as one fused pass forward and one backward; autograd splits the gradient onto the four weights
-            patch = patch_volume_train(gwc, self.patch.weight.reshape(40, 9),
-                                       torch.cat([m.weight.reshape(-1, 9) for m in (self.patch_l1, self.patch_l2, self.patch_l3)]),
-                                       PATCH_DILATION)
-        else:
-            gwc = self.patch(gwc)
-            patch = torch.cat((self.patch_l1(gwc[:, :8]), self.patch_l2(gwc[:, 8:24]), self.patch_l3(gwc[:, 24:40])), dim=1)
+        # :377-381 on the route of train_patch (DV_TRAIN_PATCH: one fused pass forward and one backward, or the nn.Conv3d
+        # statement); autograd splits the gradient onto the four weights
+        patch = patch_volume_train(gwc, self.patch.weight.reshape(40, 9),
+                                   torch.cat([m.weight.reshape(-1, 9) for m in (self.patch_l1, self.patch_l2, self.patch_l3)]),
+                                   PATCH_DILATION)
         cost_attention = _train_pair(self.dres1_att_, patch)
         cost_attention = self.dres2_att_(cost_attention)
         att_weights = _train_pair(self.classif_att_, cost_attention)

@@ -280,17 +280,6 @@ __global__ __launch_bounds__(HW_THREADS, 1) void conv2d_wgrad_cat_f16_kernel(HwA
   }
 }
 
-// dw[e] = sum over splits of ws[s][e], in split order
-__global__ __launch_bounds__(256) void wgrad_cat_f16_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                                   long long n, int splits) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    float s = ws[e];
-    for (int k = 1; k < splits; ++k) s += ws[(size_t)k * n + e];
-    dw[e] = s;
-  }
-}
-
 struct HwPlan {
   int nby, nbx, splits;
   long long nbricks;
@@ -336,10 +325,7 @@ int hw_launch(const HwArgs& a, float* dw, hipStream_t s) {
   hipLaunchKernelGGL(conv2d_wgrad_cat_f16_kernel<G>, grid, dim3(HW_THREADS), 0, s, a);
   const int rc = dv_launch_status();
   if (rc != DV_OK) return rc;
-  const long long n = (long long)a.Cout * a.Cin * G::KT;
-  const long long nb = (n + 255) / 256;
-  hipLaunchKernelGGL(wgrad_cat_f16_reduce_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, a.ws, dw, n,
-                     a.splits);
+  dv_splitk_sum(a.ws, dw, (long long)a.Cout * a.Cin * G::KT, a.splits, s);
   return dv_launch_status();
 }
 

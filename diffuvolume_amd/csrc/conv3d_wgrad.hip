@@ -151,17 +151,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void conv3d_wgrad_kernel(WgArgs a) {
   }
 }
 
-// dw[e] = sum over splits of ws[s][e], in split order
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                           long long n, int splits) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    float s = ws[e];
-    for (int k = 1; k < splits; ++k) s += ws[(size_t)k * n + e];
-    dw[e] = s;
-  }
-}
-
 struct WgPlan {
   int Do, Ho, Wo, nbz, nby, nbx, splits;
   long long nbricks;
@@ -206,10 +195,7 @@ int launch_wgrad(const float* x, const float* g, float* dw, float* ws, int B, in
   hipLaunchKernelGGL(conv3d_wgrad_kernel<G>, grid, dim3(WG_THREADS), 0, s, a);
   const int rc = dv_launch_status();
   if (rc != DV_OK) return rc;
-  const long long n = (long long)Cout * Cin * G::KT;
-  const long long nb = (n + 255) / 256;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, ws, dw, n,
-                     p.splits);
+  dv_splitk_sum(ws, dw, (long long)Cout * Cin * G::KT, p.splits, s);
   return dv_launch_status();
 }
 

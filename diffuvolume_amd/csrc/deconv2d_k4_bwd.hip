@@ -161,22 +161,6 @@ __global__ __launch_bounds__(64 * COB) void deconv2d_k4_wgrad_kernel(D2Args a) {
   }
 }
 
-// dw[e] = sum over splits of ws[s][e]: a block owns 64 elements, its wave q adds the splits of quarter q in split order,
-// the four quarters are added in quarter order through LDS -- a fixed order for a shape
-__global__ __launch_bounds__(256) void deconv2d_k4_wgrad_reduce_kernel(const float* __restrict__ ws,
-                                                                       float* __restrict__ dw, long long n, int splits) {
-  __shared__ float part[4][64];
-  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const long long e = (long long)blockIdx.x * 64 + lane;
-  const int k0 = splits * q / 4, k1 = splits * (q + 1) / 4;
-  float s = 0.f;
-  if (e < n)
-    for (int k = k0; k < k1; ++k) s += ws[(size_t)k * n + e];
-  part[q][lane] = s;
-  __syncthreads();
-  if (q == 0 && e < n) dw[e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
-}
-
 struct D2Plan {
   int cob, nt, coblocks, cigroups, nby, nbx, splits;
   long long nbricks;
@@ -254,8 +238,6 @@ extern "C" int dv_deconv2d_k4s2_wgrad_f32(const float* x, const float* g, float*
   d2_launch(p.nt, p.cob, grid, s, a);
   const int rc = dv_launch_status();
   if (rc != DV_OK) return rc;
-  const long long n = (long long)Ci * Co * 16;
-  hipLaunchKernelGGL(deconv2d_k4_wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, workspace, dw, n,
-                     p.splits);
+  dv_splitk_sum_quartered(workspace, dw, (long long)Ci * Co * 16, p.splits, s);
   return dv_launch_status();
 }

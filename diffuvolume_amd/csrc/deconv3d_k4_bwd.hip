@@ -328,17 +328,6 @@ __global__ __launch_bounds__(64 * MW * NW * KW) void deconv3d_k4_wgrad_kernel(Wg
   }
 }
 
-// dw[e] = sum over splits of ws[s][e], in split order
-__global__ __launch_bounds__(256) void k4_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                              long long n, int splits) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    float s = ws[e];
-    for (int k = 1; k < splits; ++k) s += ws[(size_t)k * n + e];
-    dw[e] = s;
-  }
-}
-
 struct WgPlan {
   int mw, nw, kw, mtiles, ntiles, nbz, nby, nbx, splits;
   long long nbricks;
@@ -443,9 +432,6 @@ extern "C" int dv_deconv3d_k4s2_wgrad_f32(const float* x, const float* g, float*
   else launch_wgrad_kernel<1, 1>(a, grid, s);
   const int rc = dv_launch_status();
   if (rc != DV_OK) return rc;
-  const long long n = (long long)Ci * Co * 64;
-  const long long nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k4_wgrad_reduce_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, workspace, dw, n,
-                     p.splits);
+  dv_splitk_sum(workspace, dw, (long long)Ci * Co * 64, p.splits, s);
   return dv_launch_status();
 }

@@ -23,6 +23,11 @@ static inline int dv_launch_status() {
 
 static inline bool dv_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// csrc/splitk_reduce.hip: dw[e] = sum over the splits of ws[s][e] (ws = [splits][n]) in a fixed order, the last launch of
+// every split-K weight gradient.  Internal; the caller returns dv_launch_status() behind the call.
+void dv_splitk_sum(const float* ws, float* dw, long long n, int splits, hipStream_t s);
+void dv_splitk_sum_quartered(const float* ws, float* dw, long long n, int splits, hipStream_t s);
+
 // exp(x) for x <= 0 (softmax terms after the max is subtracted): 2^(x*log2 e) on the hardware transcendental, with the
 // rounding error of the product carried along -- t = fl(x*L), r = (x*L - t) + x*(log2 e - L) exactly by fma, and
 // 2^(t+r) = 2^t * (1 + r ln 2) to first order (|r| <= 2^-24 |t| < 1e-5, so the next term is below 1e-10).

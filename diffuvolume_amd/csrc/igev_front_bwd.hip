@@ -119,7 +119,7 @@ __global__ __launch_bounds__(1024) void instance_norm_act_bwd_kernel(const float
 // in LDS (zero outside the image / beyond Cout, so edges need no branch in the inner loop); a thread gathers four
 // neighbouring pixels of its tap from the halo and reads g as float4 broadcasts (all lanes the same address).
 // Summation order of one dw element: one fma chain over the pixels of the split's bricks in brick order, then the splits
-// by fw_reduce_kernel (four quarters of the split range in split order each, then the quarters in order).
+// by dv_splitk_sum_quartered (four quarters of the split range in split order each, then the quarters in order).
 constexpr int FW_TY = 8, FW_TX = 16, FW_PIX = FW_TY * FW_TX;
 constexpr int FW_COB = 16, FW_THREADS = 256, FW_MAX_CIN = 4;
 constexpr int FW_TARGET_BLOCKS = 1024;                           // four blocks per CU on 256 CUs
@@ -204,22 +204,6 @@ __global__ __launch_bounds__(FW_THREADS) void conv2d_fewin_wgrad_kernel(FwArgs a
     if (co0 + n < a.Cout) out[(size_t)(co0 + n) * ntaps + t] = acc[n];
 }
 
-// dw[e] = sum over splits of ws[s][e]: a block owns 64 elements, its wave q adds the splits of quarter q in split order,
-// the four quarters are added in quarter order through LDS -- a fixed order for a shape
-__global__ __launch_bounds__(256) void fw_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, long long n,
-                                                        int splits) {
-  __shared__ float part[4][64];
-  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const long long e = (long long)blockIdx.x * 64 + lane;
-  const int k0 = splits * q / 4, k1 = splits * (q + 1) / 4;
-  float s = 0.f;
-  if (e < n)
-    for (int k = k0; k < k1; ++k) s += ws[(size_t)k * n + e];
-  part[q][lane] = s;
-  __syncthreads();
-  if (q == 0 && e < n) dw[e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
-}
-
 struct FwPlan {
   int Ho, Wo, cogroups, nby, nbx, splits;
   long long nbricks;
@@ -299,7 +283,6 @@ extern "C" int dv_conv2d_fewin_wgrad_f32(const float* x, const float* g, float* 
 #undef DV_FW
   const int rc = dv_launch_status();
   if (rc != DV_OK) return rc;
-  const long long n = (long long)Cout * Cin * k * k;
-  hipLaunchKernelGGL(fw_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, workspace, dw, n, p.splits);
+  dv_splitk_sum_quartered(workspace, dw, (long long)Cout * Cin * k * k, p.splits, s);
   return dv_launch_status();
 }

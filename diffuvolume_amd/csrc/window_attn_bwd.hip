@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256, 1) void window_attn_bwd_kernel(BwdArgs a) {
 // A = dY with B = Om; S = D*H*W), n < 128.  Split-K over chunks of 32 tokens (a chunk lies inside one batch item): a block
 // owns 128 rows m x 128 columns n and a contiguous range of chunks, four waves of 64 x 64 each (16 accumulators); both
 // tiles are staged [row][32 tokens] with the next chunk's global loads in flight during the MFMA steps.  Every split writes
-// its partial [M][128]; attn_wgrad_sum_kernel adds the splits in split order.  Row stride 34 == 2 (mod 32): the banks
+// its partial [M][128]; dv_splitk_sum adds the splits in split order.  Row stride 34 == 2 (mod 32): the banks
 // 2j + kq of a half-wave are distinct.
 constexpr int GT = 128, GK = 32, LDG = GK + 2;
 constexpr int GQ = GT * GK / 4 / 256;             // float4 per thread and tile: 4
@@ -440,16 +440,6 @@ __global__ __launch_bounds__(256, 2) void attn_wgrad_kernel(GemmArgs g) {
         out[(size_t)(64 * wm + 16 * mi + 4 * kq + r) * GT + 64 * wn + 16 * ni + j] = acc[mi][ni][r];
 }
 
-// dw[e] = sum over the splits of part[z][e], in split order
-__global__ __launch_bounds__(256) void attn_wgrad_sum_kernel(const float* __restrict__ part, float* __restrict__ dw, int n,
-                                                             int Z) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  float s = part[e];
-  for (int z = 1; z < Z; ++z) s += part[(size_t)z * n + e];
-  dw[e] = s;
-}
-
 void launch_wgrad(const float* a, const float* b, float* part, float* dw, int M, int zmax, int B, long long S,
                   hipStream_t st) {
   GemmArgs g;
@@ -459,7 +449,7 @@ void launch_wgrad(const float* a, const float* b, float* part, float* dw, int M,
   g.Z = (int)(g.T < zmax ? g.T : zmax);
   g.vec = (S % 4 == 0) && dv_aligned16(a) && dv_aligned16(b);
   hipLaunchKernelGGL(attn_wgrad_kernel, dim3((unsigned)(M / GT), (unsigned)g.Z), dim3(256), 0, st, g);
-  hipLaunchKernelGGL(attn_wgrad_sum_kernel, dim3((unsigned)(M * GT / 256)), dim3(256), 0, st, part, dw, M * GT, g.Z);
+  dv_splitk_sum(part, dw, (long long)M * GT, g.Z, st);
 }
 
 size_t wgrad_splits(int B, long long S, int zmax) {

@@ -18,22 +18,16 @@ lookups are summed by autograd.  ``DV_TRAIN_LOOKUP=torch`` swaps both functions 
 """
 from __future__ import annotations
 
-import os
+import functools
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _env, _lib
 from .profiling import timed
 from .submodule import _dev_f32, _wants_grad
 
-
-def route() -> str:
-    """'hip' (default) or 'torch' (DV_TRAIN_LOOKUP): what the training route of the lookup and of the correlation runs on."""
-    r = os.environ.get("DV_TRAIN_LOOKUP", "hip") or "hip"
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_LOOKUP must be 'hip' or 'torch', got {r!r}")
-    return r
+route = functools.partial(_env.route, "DV_TRAIN_LOOKUP")     # what the training route of the lookup and the correlation runs on
 
 
 def _checked(t, name: str) -> torch.Tensor:

@@ -24,10 +24,8 @@ def _context_upsample_shapes(disp_low, up_weights):
 def _context_upsample_launch(disp_low, up_weights, scale, apply_softmax):
     b, h, w = _context_upsample_shapes(disp_low, up_weights)
     out = torch.empty((b, 4 * h, 4 * w), dtype=torch.float32, device=disp_low.device)
-    with torch.cuda.device(disp_low.device):
-        _lib.check(_lib.load().dv_context_upsample_f32(disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h,
-                                                       w, float(scale), int(bool(apply_softmax)), _lib.stream_ptr()),
-                   "dv_context_upsample_f32")
+    _lib.launch("dv_context_upsample_f32", disp_low.device, disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h, w,
+                float(scale), int(bool(apply_softmax)))
     return out
 
 
@@ -54,11 +52,8 @@ class ContextUpsampleFn(torch.autograd.Function):
         d_w = torch.empty_like(up_weights) if need_w else None
         d_d = torch.empty_like(disp_low) if need_d else None
         sums = torch.empty((b, 9, h, w), dtype=torch.float32, device=g.device) if need_d else None
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.load().dv_context_upsample_bwd_f32(disp_low.data_ptr(), up_weights.data_ptr(), g.data_ptr(),
-                                                               _lib.ptr(d_w), _lib.ptr(d_d), _lib.ptr(sums), b, h, w,
-                                                               float(ctx.scale), int(ctx.apply_softmax), _lib.stream_ptr()),
-                       "dv_context_upsample_bwd_f32")
+        _lib.launch("dv_context_upsample_bwd_f32", g.device, disp_low.data_ptr(), up_weights.data_ptr(), g.data_ptr(),
+                    _lib.ptr(d_w), _lib.ptr(d_d), _lib.ptr(sums), b, h, w, float(ctx.scale), int(ctx.apply_softmax))
         return d_d, d_w, None, None
 
 
@@ -69,8 +64,8 @@ def context_upsample(disp_low: torch.Tensor, up_weights: torch.Tensor, scale: fl
     when autograd records and an input asks for gradients (``ContextUpsampleFn``; the reference's torch expression under
     DV_TRAIN_CONV2D=torch); otherwise the inference launch."""
     if torch.is_grad_enabled() and (disp_low.requires_grad or up_weights.requires_grad):
-        train2d._check(disp_low, "disp_low")
-        train2d._check(up_weights, "up_weights")
+        _lib.check_f32(disp_low, "disp_low")
+        _lib.check_f32(up_weights, "up_weights")
         b, h, w = _context_upsample_shapes(disp_low, up_weights)
         if train2d.route() == "torch":
             weights = F.softmax(up_weights, 1) if apply_softmax else up_weights

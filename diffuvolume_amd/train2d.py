@@ -42,24 +42,18 @@ convolutions: weight gradient on ``dv_conv2d_fewin_wgrad_f32``, no input gradien
 call: these layers run once per pair."""
 from __future__ import annotations
 
-import os
+import ctypes
+import functools
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _env, _lib
 from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan,
                         Deconv2dK4S2Plan)
-from .train3d import _check
 
-
-def route() -> str:
-    """'hip' (default) or 'torch' (DV_TRAIN_CONV2D)."""
-    r = os.environ.get("DV_TRAIN_CONV2D", "hip") or "hip"
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_CONV2D must be 'hip' or 'torch', got {r!r}")
-    return r
+route = functools.partial(_env.route, "DV_TRAIN_CONV2D")
 
 
 def conv2d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, dilation: int, cout: int) -> torch.Tensor:
@@ -67,15 +61,12 @@ def conv2d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, dilation: int, 
     gradient ``g``."""
     x, g = x.contiguous(), g.contiguous()
     b, cin, h, w = x.shape
-    lib = _lib.load()
-    n = lib.dv_conv2d_wgrad_workspace_floats(b, cin, h, w, cout, k, dilation)
-    if n == 0:
+    ws = _lib.workspace("dv_conv2d_wgrad_workspace_floats", x.device, b, cin, h, w, cout, k, dilation)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"dv_conv2d_wgrad_f32 does not take k={k} dilation={dilation}")
     dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dv_conv2d_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
-                                           cout, k, dilation, _lib.stream_ptr()), "dv_conv2d_wgrad_f32")
+    _lib.launch("dv_conv2d_wgrad_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
+                cout, k, dilation)
     return dw
 
 
@@ -85,9 +76,8 @@ def _input_grad(g: torch.Tensor, w: torch.Tensor, dilation: int) -> torch.Tensor
     if g.shape[1] == 1 and k == 3 and dilation == 1:
         b, _, h, wd = g.shape
         dx = torch.empty((b, wt.shape[0], h, wd), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.load().dv_conv2d_1in_f32(g.data_ptr(), wt.data_ptr(), 0, dx.data_ptr(), b, h, wd,
-                                                     wt.shape[0], 3, ACT_NONE, _lib.stream_ptr()), "dv_conv2d_1in_f32")
+        _lib.launch("dv_conv2d_1in_f32", g.device, g.data_ptr(), wt.data_ptr(), 0, dx.data_ptr(), b, h, wd, wt.shape[0], 3,
+                    ACT_NONE)
         return dx
     return Conv2dPlan(wt, None, dilation=dilation, act=ACT_NONE)(g)
 
@@ -95,8 +85,8 @@ def _input_grad(g: torch.Tensor, w: torch.Tensor, dilation: int) -> torch.Tensor
 class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, dilation):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         k = weight.shape[2]
         if tuple(weight.shape[2:]) != (k, k) or k not in (1, 3) or not 1 <= dilation <= 16:
             raise _lib.DiffuVolumeError(f"unsupported Conv2d: kernel {tuple(weight.shape[2:])}, dilation {dilation}")
@@ -145,7 +135,6 @@ def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) 
     concatenation of ``sources`` (1..4 tensors, never materialised) and whose output gradient is ``g``.  ``f16``: on
     ``dv_conv2d_wgrad_cat_f16`` (both operands rounded to fp16 while staged, fp32 accumulation on the fp16 MFMA, float32
     result) instead of ``dv_conv2d_wgrad_cat_f32``."""
-    import ctypes
     name = "dv_conv2d_wgrad_cat_f16" if f16 else "dv_conv2d_wgrad_cat_f32"
     sources = [t.contiguous() for t in sources]
     g = g.contiguous()
@@ -153,19 +142,15 @@ def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) 
     if not 1 <= len(sources) <= 4 or any(t.shape[0] != b or tuple(t.shape[2:]) != (h, w) for t in sources):
         raise _lib.DiffuVolumeError("conv2d_cat_weight_grad: 1..4 sources with the batch and plane of the gradient")
     for t in (*sources, g):
-        _check(t, "conv2d_cat_weight_grad operand")
+        _lib.check_f32(t, "conv2d_cat_weight_grad operand")
     ptrs = (ctypes.c_void_p * len(sources))(*[t.data_ptr() for t in sources])
     chans = (ctypes.c_int * len(sources))(*[t.shape[1] for t in sources])
-    lib = _lib.load()
-    size = lib.dv_conv2d_wgrad_cat_f16_workspace_floats if f16 else lib.dv_conv2d_wgrad_cat_workspace_floats
-    n = size(chans, len(sources), b, h, w, cout, k)
-    if n == 0:
+    size = "dv_conv2d_wgrad_cat_f16_workspace_floats" if f16 else "dv_conv2d_wgrad_cat_workspace_floats"
+    ws = _lib.workspace(size, g.device, chans, len(sources), b, h, w, cout, k)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"{name} does not take k={k}, channels {list(chans)}, Cout {cout}")
     dw = torch.empty((cout, sum(chans), k, k), dtype=torch.float32, device=g.device)
-    ws = torch.empty(n, dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(getattr(lib, name)(ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h, w, cout,
-                                      k, _lib.stream_ptr()), name)
+    _lib.launch(name, g.device, ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h, w, cout, k)
     return dw
 
 
@@ -193,9 +178,8 @@ class _InputGradPlan:
             g = grads[0].contiguous()
             b, _, h, wd = g.shape
             dx = torch.empty((b, self.cin, h, wd), dtype=torch.float32, device=g.device)
-            with torch.cuda.device(g.device):
-                _lib.check(getattr(_lib.load(), self.fn1)(g.data_ptr(), self.wt.data_ptr(), 0, dx.data_ptr(), b, h, wd,
-                                                          self.cin, 3, ACT_NONE, _lib.stream_ptr()), self.fn1)
+            _lib.launch(self.fn1, g.device, g.data_ptr(), self.wt.data_ptr(), 0, dx.data_ptr(), b, h, wd, self.cin, 3,
+                        ACT_NONE)
             return dx
         return self.plan(list(grads) if len(grads) > 1 else grads[0])
 
@@ -233,7 +217,7 @@ class TrainConvPlan:
         if conv.kernel_size != (k, k) or k not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or \
                 conv.padding != ((k - 1) // 2,) * 2 or conv.groups != 1:
             raise _lib.DiffuVolumeError(f"TrainConvPlan: 3x3 (padding 1) or 1x1, stride 1, dilation 1 only, got {conv}")
-        _check(conv.weight, "weight")
+        _lib.check_f32(conv.weight, "weight")
         self.k, self.act, self.cout, self.f16 = k, act, conv.out_channels, f16
         self.fwd = Conv2dF16Plan(conv.weight, conv.bias, act=act) if f16 else \
             Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
@@ -246,7 +230,7 @@ class ConvCatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, weight, bias, *sources):
         for t in sources:
-            _check(t, "source")
+            _lib.check_f32(t, "source")
         sources = [t.contiguous() for t in sources]
         out = plan.fwd(sources if len(sources) > 1 else sources[0])
         ctx.plan = plan
@@ -282,8 +266,8 @@ class Conv1InFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, f16=False):
-        _check(x, "disp")
-        _check(weight, "weight")
+        _lib.check_f32(x, "disp")
+        _lib.check_f32(weight, "weight")
         x, wt = x.contiguous(), weight.detach().contiguous()
         b, cin, h, w = x.shape
         k = int(wt.shape[-1])
@@ -291,9 +275,8 @@ class Conv1InFn(torch.autograd.Function):
             raise _lib.DiffuVolumeError(f"Conv1InFn: one input channel, k = 7, got {tuple(wt.shape)}")
         out = torch.empty((b, wt.shape[0], h, w), dtype=torch.float32, device=x.device)
         fn = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
-        with torch.cuda.device(x.device):
-            _lib.check(getattr(_lib.load(), fn)(x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
-                                                out.shape[1], k, ACT_RELU, _lib.stream_ptr()), fn)
+        _lib.launch(fn, x.device, x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w, out.shape[1], k,
+                    ACT_RELU)
         ctx.save_for_backward(x.half().float() if f16 else x, weight, out)
         return out
 
@@ -306,9 +289,8 @@ class Conv1InFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.load().dv_conv2d_1in_wgrad_f32(x.data_ptr(), gp.data_ptr(), dw.data_ptr(), b, h, w,
-                                                               weight.shape[0], k, _lib.stream_ptr()), "dv_conv2d_1in_wgrad_f32")
+            _lib.launch("dv_conv2d_1in_wgrad_f32", x.device, x.data_ptr(), gp.data_ptr(), dw.data_ptr(), b, h, w,
+                        weight.shape[0], k)
         if ctx.needs_input_grad[2]:
             db = gp.sum(dim=(0, 2, 3))
         if ctx.needs_input_grad[0]:
@@ -346,9 +328,7 @@ def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources, f16: bool = False) 
 
 
 def _gates(fn: str, *args) -> None:
-    with torch.cuda.device(args[0].device):
-        _lib.check(getattr(_lib.load(), fn)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
-                                            _lib.stream_ptr()), fn)
+    _lib.launch(fn, args[0].device, *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args])
 
 
 class GRUTrainPlan:
@@ -358,7 +338,7 @@ class GRUTrainPlan:
 
     def __init__(self, gru, f16: bool = False):
         for c in (gru.convz, gru.convr, gru.convq):
-            _check(c.weight, "weight")
+            _lib.check_f32(c.weight, "weight")
         self.hidden, self.f16 = gru.convz.out_channels, f16
         if f16:
             self.zr = Conv2dF16Plan(gru.convz.weight, gru.convz.bias, ACT_SIGMOID, pair=(gru.convr.weight, gru.convr.bias))
@@ -382,7 +362,7 @@ class ConvGRUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, wz, bz, wr, br, wq, bq, h, cz, cr, cq, *xs):
         for t in (h, cz, cr, cq, *xs):
-            _check(t, "ConvGRU input")
+            _lib.check_f32(t, "ConvGRU input")
         h, cz, cr, cq = (t.contiguous() for t in (h, cz, cr, cq))
         xs = [t.contiguous() for t in xs]
         z, r = plan.zr([h, *xs], residual=(cz, cr), mul=(None, None))
@@ -454,22 +434,19 @@ def conv_gru(plan, gru, h, cz, cr, cq, *xs, f16: bool = False) -> torch.Tensor:
 def deconv2d_k4_weight_grad(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """dW [Cin, Cout, 4, 4] of a ConvTranspose2d(4, stride 2, padding 1) with input ``x`` [B,Cin,H,W] and output gradient
     ``g`` [B,Cout,2H,2W]."""
-    _check(x, "x")
-    _check(g, "output gradient")
+    _lib.check_f32(x, "x")
+    _lib.check_f32(g, "output gradient")
     x, g = x.contiguous(), g.contiguous()
     b, cin, h, w = x.shape
     cout = g.shape[1]
     if g.shape[0] != b or tuple(g.shape[2:]) != (2 * h, 2 * w):
         raise _lib.DiffuVolumeError(f"deconv2d_k4_weight_grad: x {tuple(x.shape)} against g {tuple(g.shape)}")
-    lib = _lib.load()
-    n = lib.dv_deconv2d_k4s2_wgrad_workspace_floats(b, cin, h, w, cout)
-    if n == 0:
+    ws = _lib.workspace("dv_deconv2d_k4s2_wgrad_workspace_floats", x.device, b, cin, h, w, cout)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"dv_deconv2d_k4s2_wgrad_f32 does not take x {tuple(x.shape)}, Cout {cout}")
     dw = torch.empty((cin, cout, 4, 4), dtype=torch.float32, device=x.device)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dv_deconv2d_k4s2_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
-                                                  cout, _lib.stream_ptr()), "dv_deconv2d_k4s2_wgrad_f32")
+    _lib.launch("dv_deconv2d_k4s2_wgrad_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
+                cout)
     return dw
 
 
@@ -479,7 +456,7 @@ class TrainDeconvPlan:
     with the flipped, transposed parity weights."""
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
-        _check(weight, "weight")
+        _lib.check_f32(weight, "weight")
         if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4):
             raise _lib.DiffuVolumeError(f"TrainDeconvPlan: a [Cin, Cout, 4, 4] weight, got {tuple(weight.shape)}")
         self.cin, self.cout = int(weight.shape[0]), int(weight.shape[1])
@@ -492,7 +469,7 @@ class ConvTranspose2dK4Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, x, weight, bias):
-        _check(x, "x")
+        _lib.check_f32(x, "x")
         x = x.contiguous()
         if x.dim() != 4 or x.shape[1] != plan.cin or tuple(weight.shape) != (plan.cin, plan.cout, 4, 4):
             raise _lib.DiffuVolumeError(f"conv_transpose2d_k4: x {tuple(x.shape)} against weight {tuple(weight.shape)}")
@@ -553,8 +530,8 @@ class Conv2dS2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[1]:
             raise _lib.DiffuVolumeError(f"conv2d_s2: x {tuple(x.shape)} against weight {tuple(weight.shape)} (3x3 only)")
         x = x.contiguous()
@@ -592,29 +569,26 @@ def conv2d_k1s2(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     the stride-1 function on every second row and column."""
     if route() == "torch":
         return F.conv2d(x, weight, bias, stride=2)
-    _check(x, "x")
+    _lib.check_f32(x, "x")
     return Conv2dFn.apply(x[:, :, ::2, ::2].contiguous(), weight, bias, 1)
 
 
 def conv2d_fewin_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int) -> torch.Tensor:
     """dW [Cout,Cin,k,k] of a convolution with <= 4 input channels (k in {3,5,7}, stride in {1,2}, padding k/2) with input
     ``x`` and output gradient ``g``."""
-    _check(x, "x")
-    _check(g, "output gradient")
+    _lib.check_f32(x, "x")
+    _lib.check_f32(g, "output gradient")
     x, g = x.contiguous(), g.contiguous()
     b, cin, h, w = x.shape
     cout = g.shape[1]
     if g.shape[0] != b or tuple(g.shape[2:]) != ((h - 1) // stride + 1, (w - 1) // stride + 1):
         raise _lib.DiffuVolumeError(f"conv2d_fewin_weight_grad: x {tuple(x.shape)} against g {tuple(g.shape)}, stride {stride}")
-    lib = _lib.load()
-    n = lib.dv_conv2d_fewin_wgrad_workspace_floats(b, cin, h, w, cout, k, stride)
-    if n == 0:
+    ws = _lib.workspace("dv_conv2d_fewin_wgrad_workspace_floats", x.device, b, cin, h, w, cout, k, stride)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"dv_conv2d_fewin_wgrad_f32 does not take Cin={cin} k={k} stride={stride}")
     dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dv_conv2d_fewin_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
-                                                 cout, k, stride, _lib.stream_ptr()), "dv_conv2d_fewin_wgrad_f32")
+    _lib.launch("dv_conv2d_fewin_wgrad_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, h, w,
+                cout, k, stride)
     return dw
 
 
@@ -625,8 +599,8 @@ class Conv2dFewInFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         k = int(weight.shape[-1])
         if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1] or weight.shape[1] > 4 or \
                 tuple(weight.shape[2:]) != (k, k) or k not in (3, 5, 7) or stride not in (1, 2):
@@ -634,10 +608,8 @@ class Conv2dFewInFn(torch.autograd.Function):
         x, wt = x.contiguous(), weight.detach().contiguous()
         b, cin, h, w = x.shape
         out = torch.empty((b, wt.shape[0], (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dv_conv2d_fewin_f32(x.data_ptr(), wt.data_ptr(), _lib.ptr(None if bias is None else bias.detach()),
-                                                       0, 0, out.data_ptr(), b, cin, h, w, wt.shape[0], k, stride, ACT_NONE,
-                                                       _lib.stream_ptr()), "dv_conv2d_fewin_f32")
+        _lib.launch("dv_conv2d_fewin_f32", x.device, x.data_ptr(), wt.data_ptr(), _lib.ptr(None if bias is None else bias.detach()),
+                    0, 0, out.data_ptr(), b, cin, h, w, wt.shape[0], k, stride, ACT_NONE)
         ctx.save_for_backward(x)
         ctx.k, ctx.stride, ctx.has_bias = k, stride, bias is not None
         return out
@@ -669,13 +641,11 @@ class InstanceNormActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, act, eps):
-        _check(x, "x")
+        _lib.check_f32(x, "x")
         x = x.contiguous()
         b, c, h, w = x.shape
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dv_instance_norm_act_f32(x.data_ptr(), out.data_ptr(), b * c, h * w, float(eps), act,
-                                                            _lib.stream_ptr()), "dv_instance_norm_act_f32")
+        _lib.launch("dv_instance_norm_act_f32", x.device, x.data_ptr(), out.data_ptr(), b * c, h * w, float(eps), act)
         ctx.save_for_backward(x)
         ctx.act, ctx.eps = act, float(eps)
         return out
@@ -686,10 +656,8 @@ class InstanceNormActFn(torch.autograd.Function):
         g = g.contiguous()
         b, c, h, w = x.shape
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dv_instance_norm_act_bwd_f32(x.data_ptr(), g.data_ptr(), dx.data_ptr(), b * c, h * w,
-                                                                ctx.eps, ctx.act, _lib.stream_ptr()),
-                       "dv_instance_norm_act_bwd_f32")
+        _lib.launch("dv_instance_norm_act_bwd_f32", x.device, x.data_ptr(), g.data_ptr(), dx.data_ptr(), b * c, h * w, ctx.eps,
+                    ctx.act)
         return dx, None, None
 
 

@@ -18,44 +18,29 @@ BatchNorm3d and the activation behind it are ``train_norm.py``'s.  ``DV_TRAIN_CO
 everywhere on the hot path."""
 from __future__ import annotations
 
-import os
+import functools
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _env, _lib
 from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan, feature_gate
 
 
-def route() -> str:
-    """'hip' (default) or 'torch' (DV_TRAIN_CONV3D)."""
-    r = os.environ.get("DV_TRAIN_CONV3D", "hip") or "hip"
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_CONV3D must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_CONV3D")
 
 
 def conv3d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int, cout: int) -> torch.Tensor:
     """dW [Cout,Cin,k,k,k] of a cubic convolution (pad (k-1)/2) with input ``x`` and output gradient ``g``."""
     x, g = x.contiguous(), g.contiguous()
     b, cin, d, h, w = x.shape
-    lib = _lib.load()
-    n = lib.dv_conv3d_wgrad_workspace_floats(b, cin, d, h, w, cout, k, stride)
-    if n == 0:
+    ws = _lib.workspace("dv_conv3d_wgrad_workspace_floats", x.device, b, cin, d, h, w, cout, k, stride)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"dv_conv3d_wgrad_f32 does not take k={k} stride={stride}")
     dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dv_conv3d_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d, h, w,
-                                           cout, k, stride, _lib.stream_ptr()), "dv_conv3d_wgrad_f32")
+    _lib.launch("dv_conv3d_wgrad_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d, h, w,
+                cout, k, stride)
     return dw
 
 
@@ -66,8 +51,8 @@ def _plan(w: torch.Tensor, stride: int, bias: Optional[torch.Tensor] = None) -> 
 class Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         k = weight.shape[2]
         if tuple(weight.shape[2:]) != (k, k, k) or k not in (1, 3) or stride not in (1, 2) or (k == 1 and stride != 1):
             raise _lib.DiffuVolumeError(f"unsupported Conv3d: kernel {tuple(weight.shape[2:])}, stride {stride}")
@@ -103,8 +88,8 @@ class ConvTranspose3dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         if tuple(weight.shape[2:]) != (3, 3, 3):
             raise _lib.DiffuVolumeError(f"unsupported ConvTranspose3d kernel {tuple(weight.shape[2:])}")
         x = x.contiguous()
@@ -131,14 +116,11 @@ def deconv3d_k4_input_grad(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     ci = w.shape[0]
     if tuple(w.shape[1:]) != (co, 4, 4, 4) or d2 % 2 or h2 % 2 or w2 % 2:
         raise _lib.DiffuVolumeError(f"k4 input gradient: weight {tuple(w.shape)} against gradient {tuple(g.shape)}")
-    lib = _lib.load()
-    wp = torch.empty(lib.dv_deconv3d_k4s2_dgrad_packed_floats(ci, co), dtype=torch.float32, device=g.device)
+    wp = _lib.workspace("dv_deconv3d_k4s2_dgrad_packed_floats", g.device, ci, co)
     dx = torch.empty((b, ci, d2 // 2, h2 // 2, w2 // 2), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.dv_deconv3d_k4s2_dgrad_pack_weights_f32(w.data_ptr(), wp.data_ptr(), ci, co, _lib.stream_ptr()),
-                   "dv_deconv3d_k4s2_dgrad_pack_weights_f32")
-        _lib.check(lib.dv_deconv3d_k4s2_dgrad_f32(g.data_ptr(), wp.data_ptr(), dx.data_ptr(), b, ci, d2 // 2, h2 // 2,
-                                                  w2 // 2, co, _lib.stream_ptr()), "dv_deconv3d_k4s2_dgrad_f32")
+    _lib.launch("dv_deconv3d_k4s2_dgrad_pack_weights_f32", g.device, w.data_ptr(), wp.data_ptr(), ci, co)
+    _lib.launch("dv_deconv3d_k4s2_dgrad_f32", g.device, g.data_ptr(), wp.data_ptr(), dx.data_ptr(), b, ci, d2 // 2, h2 // 2,
+                w2 // 2, co)
     return dx
 
 
@@ -149,15 +131,12 @@ def deconv3d_k4_weight_grad(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     co = g.shape[1]
     if tuple(g.shape) != (b, co, 2 * d, 2 * h, 2 * w):
         raise _lib.DiffuVolumeError(f"k4 weight gradient: input {tuple(x.shape)} against gradient {tuple(g.shape)}")
-    lib = _lib.load()
-    n = lib.dv_deconv3d_k4s2_wgrad_workspace_floats(b, ci, d, h, w, co)
-    if n == 0:
+    ws = _lib.workspace("dv_deconv3d_k4s2_wgrad_workspace_floats", x.device, b, ci, d, h, w, co)
+    if ws is None:
         raise _lib.DiffuVolumeError(f"dv_deconv3d_k4s2_wgrad_f32 does not take the shape {tuple(x.shape)}")
     dw = torch.empty((ci, co, 4, 4, 4), dtype=torch.float32, device=x.device)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dv_deconv3d_k4s2_wgrad_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, ci, d, h,
-                                                  w, co, _lib.stream_ptr()), "dv_deconv3d_k4s2_wgrad_f32")
+    _lib.launch("dv_deconv3d_k4s2_wgrad_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, ci, d, h,
+                w, co)
     return dw
 
 
@@ -166,8 +145,8 @@ class ConvTranspose3dK4Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight):
-        _check(x, "x")
-        _check(weight, "weight")
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
         if weight.dim() != 5 or tuple(weight.shape[2:]) != (4, 4, 4):
             raise _lib.DiffuVolumeError(f"unsupported ConvTranspose3d kernel {tuple(weight.shape[2:])}")
         x = x.contiguous()
@@ -190,14 +169,10 @@ def feature_gate_grads(cv: torch.Tensor, logit: torch.Tensor, g: torch.Tensor):
     """(dcv, dlogit) of ``sigmoid(logit).unsqueeze(2) * cv`` from the output gradient ``g``."""
     cv, logit, g = cv.contiguous(), logit.contiguous(), g.contiguous()
     b, c, d, h, w = cv.shape
-    lib = _lib.load()
     dcv, dlogit = torch.empty_like(cv), torch.empty_like(logit)
-    n = lib.dv_feature_gate_bwd_workspace_floats(b, c, d, h, w)
-    ws = torch.empty(n, dtype=torch.float32, device=cv.device) if n else None
-    with torch.cuda.device(cv.device):
-        _lib.check(lib.dv_feature_gate_bwd_f32(cv.data_ptr(), logit.data_ptr(), g.data_ptr(), dcv.data_ptr(),
-                                               dlogit.data_ptr(), _lib.ptr(ws), b, c, d, h, w, _lib.stream_ptr()),
-                   "dv_feature_gate_bwd_f32")
+    ws = _lib.workspace("dv_feature_gate_bwd_workspace_floats", cv.device, b, c, d, h, w)
+    _lib.launch("dv_feature_gate_bwd_f32", cv.device, cv.data_ptr(), logit.data_ptr(), g.data_ptr(), dcv.data_ptr(),
+                dlogit.data_ptr(), _lib.ptr(ws), b, c, d, h, w)
     return dcv, dlogit
 
 
@@ -206,8 +181,8 @@ class FeatureGateFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cv, logit):
-        _check(cv, "cv")
-        _check(logit, "logit")
+        _lib.check_f32(cv, "cv")
+        _lib.check_f32(logit, "logit")
         if cv.dim() != 5 or tuple(logit.shape) != (cv.shape[0], cv.shape[1], cv.shape[3], cv.shape[4]):
             raise _lib.DiffuVolumeError(f"gate logits {tuple(logit.shape)} do not match volume {tuple(cv.shape)}")
         cv, logit = cv.contiguous(), logit.contiguous()

@@ -14,7 +14,7 @@ There is no double backward.  ``DV_TRAIN_ATTN=torch`` routes the function to the
 CPU tensors raise, as everywhere on the hot path."""
 from __future__ import annotations
 
-import os
+import functools
 
 import torch
 import torch.nn.functional as F
@@ -23,22 +23,7 @@ from torch.autograd.function import once_differentiable
 from . import _env, _lib, train3d
 
 
-def route() -> str:
-    """'hip' or 'torch' (DV_TRAIN_ATTN; the default is the one of _env.KNOBS)."""
-    default = _env.KNOBS["DV_TRAIN_ATTN"][0]
-    r = os.environ.get("DV_TRAIN_ATTN", default) or default
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_ATTN must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_ATTN")
 
 
 def _statement(x, qkv_w, qkv_b, proj_w, proj_b, heads, block: int = 4):
@@ -80,11 +65,8 @@ class WindowAttentionFn(torch.autograd.Function):
         x, qkv_w, qkv_b, proj_w, proj_b = (t.contiguous() for t in (x, qkv_w, qkv_b, proj_w, proj_b))
         b, c, d, h, w = x.shape
         out = torch.empty_like(x)
-        lib = _lib.load()
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dv_window_attn3d_f32(x.data_ptr(), qkv_w.data_ptr(), qkv_b.data_ptr(), proj_w.data_ptr(),
-                                                proj_b.data_ptr(), out.data_ptr(), b, c, d, h, w, heads, _lib.stream_ptr()),
-                       "dv_window_attn3d_f32")
+        _lib.launch("dv_window_attn3d_f32", x.device, x.data_ptr(), qkv_w.data_ptr(), qkv_b.data_ptr(), proj_w.data_ptr(),
+                    proj_b.data_ptr(), out.data_ptr(), b, c, d, h, w, heads)
         ctx.save_for_backward(x, qkv_w, qkv_b, proj_w, proj_b)
         ctx.heads = heads
         return out
@@ -96,19 +78,15 @@ class WindowAttentionFn(torch.autograd.Function):
         want = ctx.needs_input_grad[:5]
         if not any(want):
             return None, None, None, None, None, None
-        _check(dout, "grad_output")
+        _lib.check_f32(dout, "grad_output")
         dout = dout.contiguous()
         b, c, d, h, w = x.shape
-        lib = _lib.load()
         grads = [torch.empty_like(t) if wanted else None for t, wanted in zip((x, qkv_w, qkv_b, proj_w, proj_b), want)]
         ws = None
         if want[1] or want[2] or want[3]:
-            ws = torch.empty(lib.dv_window_attn3d_bwd_workspace_floats(b, c, d, h, w, ctx.heads), dtype=torch.float32,
-                             device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dv_window_attn3d_bwd_f32(x.data_ptr(), qkv_w.data_ptr(), qkv_b.data_ptr(), proj_w.data_ptr(),
-                                                    dout.data_ptr(), *(_lib.ptr(g) for g in grads), _lib.ptr(ws),
-                                                    b, c, d, h, w, ctx.heads, _lib.stream_ptr()), "dv_window_attn3d_bwd_f32")
+            ws = _lib.workspace("dv_window_attn3d_bwd_workspace_floats", x.device, b, c, d, h, w, ctx.heads)
+        _lib.launch("dv_window_attn3d_bwd_f32", x.device, x.data_ptr(), qkv_w.data_ptr(), qkv_b.data_ptr(), proj_w.data_ptr(),
+                    dout.data_ptr(), *(_lib.ptr(g) for g in grads), _lib.ptr(ws), b, c, d, h, w, ctx.heads)
         return (*grads, None)
 
 
@@ -118,7 +96,7 @@ def window_attention_train(x: torch.Tensor, qkv_w: torch.Tensor, qkv_b: torch.Te
     ([C,C] or [C,C,1,1,1]) and ``final1x1.bias`` [C], differentiable in all five.  Returns a fresh tensor."""
     r = route()
     for name, t in (("x", x), ("qkv_w", qkv_w), ("qkv_b", qkv_b), ("proj_w", proj_w), ("proj_b", proj_b)):
-        _check(t, name)
+        _lib.check_f32(t, name)
     if x.dim() != 5:
         raise RuntimeError(f"x must be [B,C,D,H,W], got {tuple(x.shape)}")
     c = x.shape[1]

@@ -19,7 +19,7 @@ CPU tensors raise, as everywhere on the hot path.
 ``num_batches_tracked`` and keeps the PyTorch statement for whatever lies outside the kernel's case."""
 from __future__ import annotations
 
-import os
+import functools
 from typing import Optional
 
 import torch
@@ -31,22 +31,7 @@ from . import _env, _lib
 ACTS = {"none": 0, "relu": 1, "mish": 2}            # DV_ACT_NONE / DV_ACT_RELU / DV_ACT_MISH
 
 
-def route() -> str:
-    """'hip' or 'torch' (DV_TRAIN_NORM; the default is the one of _env.KNOBS)."""
-    default = _env.KNOBS["DV_TRAIN_NORM"][0]
-    r = os.environ.get("DV_TRAIN_NORM", default) or default
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_NORM must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_NORM")
 
 
 def _statement(x, weight, bias, running_mean, running_var, momentum, eps, act, skip):
@@ -75,18 +60,14 @@ class BatchNormActFn(torch.autograd.Function):
         x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
         skip = None if skip is None else skip.contiguous()
         b, c, s = _bcs(x)
-        lib = _lib.load()
         mean = torch.empty(c, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
         y = torch.empty_like(x)
-        ws = torch.empty(lib.dv_bn3d_train_workspace_floats(b, c, s), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dv_bn3d_stats_f32(x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _lib.ptr(running_mean),
-                                             _lib.ptr(running_var), ws.data_ptr(), b, c, s, float(momentum), float(eps),
-                                             _lib.stream_ptr()), "dv_bn3d_stats_f32")
-            _lib.check(lib.dv_bn3d_apply_act_f32(x.data_ptr(), _lib.ptr(skip), mean.data_ptr(), invstd.data_ptr(),
-                                                 weight.data_ptr(), bias.data_ptr(), y.data_ptr(), b, c, s, act,
-                                                 _lib.stream_ptr()), "dv_bn3d_apply_act_f32")
+        ws = _lib.workspace("dv_bn3d_train_workspace_floats", x.device, b, c, s)
+        _lib.launch("dv_bn3d_stats_f32", x.device, x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _lib.ptr(running_mean),
+                    _lib.ptr(running_var), _lib.ptr(ws), b, c, s, float(momentum), float(eps))
+        _lib.launch("dv_bn3d_apply_act_f32", x.device, x.data_ptr(), _lib.ptr(skip), mean.data_ptr(), invstd.data_ptr(),
+                    weight.data_ptr(), bias.data_ptr(), y.data_ptr(), b, c, s, act)
         ctx.save_for_backward(x, skip, mean, invstd, weight, bias)
         ctx.act = act
         return y
@@ -100,20 +81,17 @@ class BatchNormActFn(torch.autograd.Function):
         none = (None,) * 9
         if not (want_x or want_w or want_b or want_s):
             return none
-        _check(dy, "grad_output")
+        _lib.check_f32(dy, "grad_output")
         dy = dy.contiguous()
         b, c, s = _bcs(x)
-        lib = _lib.load()
         dx = torch.empty_like(x) if want_x else None
         dskip = torch.empty_like(x) if want_s else None
         dgamma = torch.empty_like(mean) if want_w else None
         dbeta = torch.empty_like(mean) if want_b else None
-        ws = torch.empty(lib.dv_bn3d_train_workspace_floats(b, c, s), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dv_bn3d_act_bwd_f32(dy.data_ptr(), x.data_ptr(), _lib.ptr(skip), mean.data_ptr(),
-                                               invstd.data_ptr(), weight.data_ptr(), bias.data_ptr(), _lib.ptr(dx),
-                                               _lib.ptr(dskip), _lib.ptr(dgamma), _lib.ptr(dbeta), ws.data_ptr(), b, c, s,
-                                               ctx.act, _lib.stream_ptr()), "dv_bn3d_act_bwd_f32")
+        ws = _lib.workspace("dv_bn3d_train_workspace_floats", x.device, b, c, s)
+        _lib.launch("dv_bn3d_act_bwd_f32", x.device, dy.data_ptr(), x.data_ptr(), _lib.ptr(skip), mean.data_ptr(),
+                    invstd.data_ptr(), weight.data_ptr(), bias.data_ptr(), _lib.ptr(dx), _lib.ptr(dskip), _lib.ptr(dgamma),
+                    _lib.ptr(dbeta), _lib.ptr(ws), b, c, s, ctx.act)
         return dx, dgamma, dbeta, None, None, dskip, None, None, None
 
 
@@ -131,7 +109,7 @@ def batch_norm_act_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tens
         raise RuntimeError("running_mean and running_var go together")
     for name, t in named.items():
         if t is not None or name in ("x", "weight", "bias"):
-            _check(t, name)
+            _lib.check_f32(t, name)
     if x.dim() < 2:
         raise RuntimeError(f"x must be [B,C,...], got {tuple(x.shape)}")
     c = x.shape[1]

@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import os
 from typing import Sequence
 
 import torch
@@ -30,22 +29,7 @@ from torch.autograd.function import once_differentiable
 from . import _env, _lib
 
 
-def route() -> str:
-    """'hip' or 'torch' (DV_TRAIN_PATCH; the default is the one of _env.KNOBS)."""
-    default = _env.KNOBS["DV_TRAIN_PATCH"][0]
-    r = os.environ.get("DV_TRAIN_PATCH", default) or default
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_PATCH must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_PATCH")
 
 
 @functools.lru_cache(maxsize=16)
@@ -86,12 +70,9 @@ class PatchVolumeFn(torch.autograd.Function):
         b, g, d, h, w = gwc.shape
         n, g0, ng, dl, _ = _runs(dilation)
         out = torch.empty_like(gwc)
-        lib = _lib.load()
-        with torch.cuda.device(gwc.device):
-            table = _dilation_table(dilation, gwc.device)
-            _lib.check(lib.dv_patch_volume_runs_f32(gwc.data_ptr(), w1.data_ptr(), w2.data_ptr(), table.data_ptr(),
-                                                    out.data_ptr(), b, g, d, h, w, n, g0, ng, dl, _lib.stream_ptr()),
-                       "dv_patch_volume_runs_f32")
+        table = _dilation_table(dilation, gwc.device)
+        _lib.launch("dv_patch_volume_runs_f32", gwc.device, gwc.data_ptr(), w1.data_ptr(), w2.data_ptr(), table.data_ptr(),
+                    out.data_ptr(), b, g, d, h, w, n, g0, ng, dl)
         ctx.save_for_backward(gwc, w1, w2)
         ctx.dilation = dilation
         return out
@@ -103,21 +84,18 @@ class PatchVolumeFn(torch.autograd.Function):
         want_x, want_w1, want_w2 = ctx.needs_input_grad[:3]
         if not (want_x or want_w1 or want_w2):
             return None, None, None, None
-        _check(dout, "grad_output")
+        _lib.check_f32(dout, "grad_output")
         dout = dout.contiguous()
         b, g, d, h, w = gwc.shape
         n, g0, ng, dl, _ = _runs(ctx.dilation)
-        lib = _lib.load()
         dgwc = torch.empty_like(gwc) if want_x else None
         dw1 = torch.empty_like(w1) if want_w1 else None
         dw2 = torch.empty_like(w2) if want_w2 else None
         ws = None
         if want_w1 or want_w2:
-            ws = torch.empty(lib.dv_patch_volume_bwd_workspace_floats(b, g, d, h, w), dtype=torch.float32, device=gwc.device)
-        with torch.cuda.device(gwc.device):
-            _lib.check(lib.dv_patch_volume_bwd_f32(gwc.data_ptr(), w1.data_ptr(), w2.data_ptr(), dout.data_ptr(),
-                                                   _lib.ptr(dgwc), _lib.ptr(dw1), _lib.ptr(dw2), _lib.ptr(ws), b, g, d, h, w,
-                                                   n, g0, ng, dl, _lib.stream_ptr()), "dv_patch_volume_bwd_f32")
+            ws = _lib.workspace("dv_patch_volume_bwd_workspace_floats", gwc.device, b, g, d, h, w)
+        _lib.launch("dv_patch_volume_bwd_f32", gwc.device, gwc.data_ptr(), w1.data_ptr(), w2.data_ptr(), dout.data_ptr(),
+                    _lib.ptr(dgwc), _lib.ptr(dw1), _lib.ptr(dw2), _lib.ptr(ws), b, g, d, h, w, n, g0, ng, dl)
         return dgwc, dw1, dw2, None
 
 
@@ -126,7 +104,7 @@ def patch_volume_train(gwc: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, di
     sequence of G ints in 1..3, differentiable in gwc, w1 and w2.  Returns a fresh tensor."""
     r = route()
     for name, t in (("gwc", gwc), ("w1", w1), ("w2", w2)):
-        _check(t, name)
+        _lib.check_f32(t, name)
     if gwc.dim() != 5:
         raise RuntimeError(f"gwc must be [B,G,D,H,W], got {tuple(gwc.shape)}")
     g = gwc.shape[1]

@@ -15,7 +15,7 @@ There is no double backward.  ``DV_TRAIN_REFINE=torch`` routes the function to t
 ``groupwise_corr_pm`` of pwcnet_ddim.py) instead (A/B runs, tests).  CPU tensors raise, as everywhere on the hot path."""
 from __future__ import annotations
 
-import os
+import functools
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -24,23 +24,7 @@ from . import _env, _lib
 
 MAXSHIFT, CMAX = 24, 32               # what csrc/warp_corr.hip implements (as csrc/refine_inputs.hip)
 
-
-def route() -> str:
-    """'hip' or 'torch' (DV_TRAIN_REFINE; the default is the one of _env.KNOBS)."""
-    default = _env.KNOBS["DV_TRAIN_REFINE"][0]
-    r = os.environ.get("DV_TRAIN_REFINE", default) or default
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_REFINE must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_REFINE")
 
 
 def warp_corr_grad(left, right, disp, g_diff, g_corr, maxshift=MAXSHIFT, want_left=True, want_right=True, want_disp=True):
@@ -53,14 +37,10 @@ def warp_corr_grad(left, right, disp, g_diff, g_corr, maxshift=MAXSHIFT, want_le
     ddisp = torch.empty_like(disp) if want_disp else None
     if left.numel() == 0:
         return tuple(None if t is None else t.zero_() for t in (dleft, dright, ddisp))
-    lib = _lib.load()
-    n = lib.dv_warp_corr_bwd_workspace_floats(b, c, h, w) if want_right else 0
-    ws = torch.empty(n, dtype=torch.float32, device=left.device) if n else None
-    with torch.cuda.device(left.device):
-        _lib.check(lib.dv_warp_corr_bwd_f32(left.data_ptr(), right.data_ptr(), disp.data_ptr(), g_diff.data_ptr(),
-                                            g_corr.data_ptr(), _lib.ptr(dleft), _lib.ptr(dright), _lib.ptr(ddisp),
-                                            _lib.ptr(ws), b, c, h, w, int(maxshift), _lib.stream_ptr()),
-                   "dv_warp_corr_bwd_f32")
+    ws = _lib.workspace("dv_warp_corr_bwd_workspace_floats", left.device, b, c, h, w) if want_right else None
+    _lib.launch("dv_warp_corr_bwd_f32", left.device, left.data_ptr(), right.data_ptr(), disp.data_ptr(), g_diff.data_ptr(),
+                g_corr.data_ptr(), _lib.ptr(dleft), _lib.ptr(dright), _lib.ptr(ddisp), _lib.ptr(ws), b, c, h, w,
+                int(maxshift))
     return dleft, dright, ddisp
 
 
@@ -74,10 +54,8 @@ class WarpCorrFn(torch.autograd.Function):
         diff = torch.empty_like(left)
         corr = torch.empty((b, 2 * maxshift + 1, h, w), dtype=torch.float32, device=left.device)
         if left.numel():
-            with torch.cuda.device(left.device):
-                _lib.check(_lib.load().dv_warp_corr_f32(left.data_ptr(), right.data_ptr(), disp.data_ptr(),
-                                                        diff.data_ptr(), corr.data_ptr(), b, c, h, w, maxshift,
-                                                        _lib.stream_ptr()), "dv_warp_corr_f32")
+            _lib.launch("dv_warp_corr_f32", left.device, left.data_ptr(), right.data_ptr(), disp.data_ptr(), diff.data_ptr(),
+                        corr.data_ptr(), b, c, h, w, maxshift)
         else:
             corr.zero_()
         ctx.save_for_backward(left, right, disp)
@@ -91,8 +69,8 @@ class WarpCorrFn(torch.autograd.Function):
         want = ctx.needs_input_grad[:3]
         if not any(want):
             return None, None, None, None
-        _check(g_diff, "grad_diff")
-        _check(g_corr, "grad_corr")
+        _lib.check_f32(g_diff, "grad_diff")
+        _lib.check_f32(g_corr, "grad_corr")
         dleft, dright, ddisp = warp_corr_grad(left, right, disp, g_diff, g_corr, ctx.maxshift, *want)
         return dleft, dright, ddisp, None
 
@@ -101,9 +79,9 @@ def warp_corr_train(left: torch.Tensor, right: torch.Tensor, disp: torch.Tensor,
     """left, right [B,C,H,W], disp [B,1,H,W] -> (left - warp(right, disp) [B,C,H,W], their +-maxshift correlation
     [B,2*maxshift+1,H,W]), differentiable with respect to all three inputs."""
     r = route()
-    _check(left, "left")
-    _check(right, "right")
-    _check(disp, "disp")
+    _lib.check_f32(left, "left")
+    _lib.check_f32(right, "right")
+    _lib.check_f32(disp, "disp")
     if left.dim() != 4 or left.shape != right.shape:
         raise RuntimeError(f"feature shapes differ or are not 4-D: {tuple(left.shape)} vs {tuple(right.shape)}")
     b, c, h, w = left.shape

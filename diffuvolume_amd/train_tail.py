@@ -12,28 +12,15 @@ There is no double backward.  ``DV_TRAIN_TAIL=torch`` routes the function to the
 tests).  CPU tensors raise, as everywhere on the hot path."""
 from __future__ import annotations
 
-import os
+import functools
 
 import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _env, _lib
 
-
-def route() -> str:
-    """'hip' (default) or 'torch' (DV_TRAIN_TAIL)."""
-    r = os.environ.get("DV_TRAIN_TAIL", "hip") or "hip"
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_TAIL must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_TAIL")
 
 
 def torch_tail(cost: torch.Tensor, size, align_corners: bool = False) -> torch.Tensor:
@@ -49,15 +36,10 @@ def regress_tail_grad(cost: torch.Tensor, disp: torch.Tensor, grad_disp: torch.T
     """dcost [B,D,h,w] from cost [B,D,h,w], the forward's disp [B,4h,4w] and its gradient."""
     cost, disp, grad_disp = cost.contiguous(), disp.contiguous(), grad_disp.contiguous()
     b, d, h, w = cost.shape
-    lib = _lib.load()
     dcost = torch.empty_like(cost)
-    n = lib.dv_upsample_softmax_regress_bwd_workspace_floats(b, d, h, w)
-    ws = torch.empty(n, dtype=torch.float32, device=cost.device) if n else None
-    with torch.cuda.device(cost.device):
-        _lib.check(lib.dv_upsample_softmax_regress_bwd_f32(cost.data_ptr(), disp.data_ptr(), grad_disp.data_ptr(),
-                                                           dcost.data_ptr(), _lib.ptr(ws), b, d, h, w,
-                                                           int(bool(align_corners)), _lib.stream_ptr()),
-                   "dv_upsample_softmax_regress_bwd_f32")
+    ws = _lib.workspace("dv_upsample_softmax_regress_bwd_workspace_floats", cost.device, b, d, h, w)
+    _lib.launch("dv_upsample_softmax_regress_bwd_f32", cost.device, cost.data_ptr(), disp.data_ptr(), grad_disp.data_ptr(),
+                dcost.data_ptr(), _lib.ptr(ws), b, d, h, w, int(bool(align_corners)))
     return dcost
 
 
@@ -66,15 +48,13 @@ class UpsampleSoftmaxRegressFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cost, align_corners):
-        _check(cost, "cost")
+        _lib.check_f32(cost, "cost")
         cost = cost.contiguous()
         b, d, h, w = cost.shape
         disp = torch.empty((b, 4 * h, 4 * w), dtype=torch.float32, device=cost.device)
         if disp.numel():
-            with torch.cuda.device(cost.device):
-                _lib.check(_lib.load().dv_upsample_softmax_regress_f32(cost.data_ptr(), disp.data_ptr(), None, b, d, h, w,
-                                                                       int(align_corners), _lib.stream_ptr()),
-                           "dv_upsample_softmax_regress_f32")
+            _lib.launch("dv_upsample_softmax_regress_f32", cost.device, cost.data_ptr(), disp.data_ptr(), None, b, d, h, w,
+                        int(align_corners))
         ctx.save_for_backward(cost, disp)
         ctx.align_corners = align_corners
         return disp
@@ -85,7 +65,7 @@ class UpsampleSoftmaxRegressFn(torch.autograd.Function):
         cost, disp = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return None, None
-        _check(g, "grad_disp")
+        _lib.check_f32(g, "grad_disp")
         if not cost.numel():
             return torch.zeros_like(cost), None
         return regress_tail_grad(cost, disp, g, ctx.align_corners), None
@@ -94,7 +74,7 @@ class UpsampleSoftmaxRegressFn(torch.autograd.Function):
 def upsample_softmax_regress_train(cost: torch.Tensor, align_corners: bool = False) -> torch.Tensor:
     """cost [B,1,D,h,w] (or [B,D,h,w]) -> disp [B,4h,4w], differentiable with respect to cost."""
     r = route()
-    _check(cost, "cost")
+    _lib.check_f32(cost, "cost")
     if cost.dim() == 5:
         if cost.shape[1] != 1:
             raise RuntimeError("cost must have one channel")

@@ -13,34 +13,19 @@ There is no double backward.  ``DV_TRAIN_VOLUME=torch`` routes both to the PyTor
 (A/B runs, tests).  CPU tensors raise, as everywhere on the hot path."""
 from __future__ import annotations
 
-import os
+import functools
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _env, _lib
 
-
-def route() -> str:
-    """'hip' (default) or 'torch' (DV_TRAIN_VOLUME)."""
-    r = os.environ.get("DV_TRAIN_VOLUME", "hip") or "hip"
-    if r not in ("hip", "torch"):
-        raise ValueError(f"DV_TRAIN_VOLUME must be 'hip' or 'torch', got {r!r}")
-    return r
-
-
-def _check(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise _lib.DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+route = functools.partial(_env.route, "DV_TRAIN_VOLUME")
 
 
 def _check_pair(ref, tgt):
-    _check(ref, "refimg_fea")
-    _check(tgt, "targetimg_fea")
+    _lib.check_f32(ref, "refimg_fea")
+    _lib.check_f32(tgt, "targetimg_fea")
     if ref.dim() != 4 or ref.shape != tgt.shape:
         raise RuntimeError(f"feature shapes differ or are not 4-D: {tuple(ref.shape)} vs {tuple(tgt.shape)}")
 
@@ -53,10 +38,8 @@ def gwc_volume_grad(ref, tgt, dvol, num_groups, want_ref=True, want_tgt=True):
     dtgt = torch.empty_like(tgt) if want_tgt else None
     if dvol.numel() == 0:
         return (None if dref is None else dref.zero_()), (None if dtgt is None else dtgt.zero_())
-    with torch.cuda.device(ref.device):
-        _lib.check(_lib.load().dv_gwc_volume_bwd_f32(ref.data_ptr(), tgt.data_ptr(), dvol.data_ptr(), _lib.ptr(dref),
-                                                     _lib.ptr(dtgt), b, c, h, w, dvol.shape[2], num_groups,
-                                                     _lib.stream_ptr()), "dv_gwc_volume_bwd_f32")
+    _lib.launch("dv_gwc_volume_bwd_f32", ref.device, ref.data_ptr(), tgt.data_ptr(), dvol.data_ptr(), _lib.ptr(dref),
+                _lib.ptr(dtgt), b, c, h, w, dvol.shape[2], num_groups)
     return dref, dtgt
 
 
@@ -71,13 +54,9 @@ def concat_volume_grad(ref, tgt, scale, dvol, zero_left=False, want_ref=True, wa
     ds = torch.empty_like(scale) if want_scale else None
     if dvol.numel() == 0:
         return tuple(None if t is None else t.zero_() for t in (dref, dtgt, ds))
-    lib = _lib.load()
-    n = lib.dv_concat_volume_bwd_workspace_floats(b, c, h, w, d) if want_scale else 0
-    ws = torch.empty(n, dtype=torch.float32, device=ref.device) if n else None
-    with torch.cuda.device(ref.device):
-        _lib.check(lib.dv_concat_volume_bwd_f32(ref.data_ptr(), tgt.data_ptr(), _lib.ptr(scale), dvol.data_ptr(),
-                                                _lib.ptr(dref), _lib.ptr(dtgt), _lib.ptr(ds), _lib.ptr(ws), b, c, h, w, d,
-                                                int(bool(zero_left)), _lib.stream_ptr()), "dv_concat_volume_bwd_f32")
+    ws = _lib.workspace("dv_concat_volume_bwd_workspace_floats", ref.device, b, c, h, w, d) if want_scale else None
+    _lib.launch("dv_concat_volume_bwd_f32", ref.device, ref.data_ptr(), tgt.data_ptr(), _lib.ptr(scale), dvol.data_ptr(),
+                _lib.ptr(dref), _lib.ptr(dtgt), _lib.ptr(ds), _lib.ptr(ws), b, c, h, w, d, int(bool(zero_left)))
     return dref, dtgt, ds
 
 
@@ -90,9 +69,8 @@ class GwcVolumeFn(torch.autograd.Function):
         b, c, h, w = ref.shape
         out = torch.empty((b, num_groups, maxdisp, h, w), dtype=torch.float32, device=ref.device)
         if out.numel():
-            with torch.cuda.device(ref.device):
-                _lib.check(_lib.load().dv_gwc_volume_f32(ref.data_ptr(), tgt.data_ptr(), out.data_ptr(), b, c, h, w,
-                                                         maxdisp, num_groups, _lib.stream_ptr()), "dv_gwc_volume_f32")
+            _lib.launch("dv_gwc_volume_f32", ref.device, ref.data_ptr(), tgt.data_ptr(), out.data_ptr(), b, c, h, w, maxdisp,
+                        num_groups)
         ctx.save_for_backward(ref, tgt)
         ctx.num_groups = num_groups
         return out
@@ -104,7 +82,7 @@ class GwcVolumeFn(torch.autograd.Function):
         want_ref, want_tgt = ctx.needs_input_grad[:2]
         if not (want_ref or want_tgt):
             return None, None, None, None
-        _check(g, "grad_volume")
+        _lib.check_f32(g, "grad_volume")
         dref, dtgt = gwc_volume_grad(ref, tgt, g, ctx.num_groups, want_ref, want_tgt)
         return dref, dtgt, None, None
 
@@ -118,17 +96,12 @@ class ConcatVolumeFn(torch.autograd.Function):
         scale = None if scale is None else scale.contiguous()
         b, c, h, w = ref.shape
         out = torch.empty((b, 2 * c, maxdisp, h, w), dtype=torch.float32, device=ref.device)
-        if out.numel():
-            lib = _lib.load()
-            with torch.cuda.device(ref.device):
-                if scale is None:
-                    _lib.check(lib.dv_concat_volume_f32(ref.data_ptr(), tgt.data_ptr(), out.data_ptr(), b, c, h, w,
-                                                        maxdisp, int(zero_left), _lib.stream_ptr()),
-                               "dv_concat_volume_f32")
-                else:
-                    _lib.check(lib.dv_concat_prob_volume_f32(ref.data_ptr(), tgt.data_ptr(), scale.data_ptr(),
-                                                             out.data_ptr(), b, c, h, w, maxdisp, _lib.stream_ptr()),
-                               "dv_concat_prob_volume_f32")
+        if out.numel() and scale is None:
+            _lib.launch("dv_concat_volume_f32", ref.device, ref.data_ptr(), tgt.data_ptr(), out.data_ptr(), b, c, h, w,
+                        maxdisp, int(zero_left))
+        elif out.numel():
+            _lib.launch("dv_concat_prob_volume_f32", ref.device, ref.data_ptr(), tgt.data_ptr(), scale.data_ptr(),
+                        out.data_ptr(), b, c, h, w, maxdisp)
         if scale is None:
             ctx.save_for_backward(ref, tgt)
         else:
@@ -145,7 +118,7 @@ class ConcatVolumeFn(torch.autograd.Function):
         want_scale = want_scale and scale is not None
         if not (want_ref or want_tgt or want_scale):
             return None, None, None, None, None
-        _check(g, "grad_volume")
+        _lib.check_f32(g, "grad_volume")
         dref, dtgt, ds = concat_volume_grad(ref, tgt, scale, g, ctx.zero_left, want_ref, want_tgt, want_scale)
         return dref, dtgt, ds, None, None
 
@@ -169,7 +142,7 @@ def build_concat_volume_train(ref: torch.Tensor, tgt: torch.Tensor, maxdisp: int
     _check_pair(ref, tgt)
     zero_left = bool(zero_left)
     if scale is not None:
-        _check(scale, "scale")
+        _lib.check_f32(scale, "scale")
         b, _, h, w = ref.shape
         if tuple(scale.shape) != (b, maxdisp, h, w):
             raise RuntimeError(f"scale must be {(b, maxdisp, h, w)}, got {tuple(scale.shape)}")

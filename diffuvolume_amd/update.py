@@ -388,7 +388,7 @@ class BasicMultiUpdateBlock(_Planned):
     def _forward_train(self, net, inp, corr, disp, iter04, iter08, iter16, update, mask):
         """The reference's forward (update.py:121-142) on the differentiable route, one stream.  The plans of the whole
         block follow the weight key: an optimizer step between two calls drops them here."""
-        from .train2d import _check, conv_cat
+        from .train2d import conv_cat
         f16, slot = _train_entry(self)
         if f16:                   # an autocast caller's fp16 tensors: float32 once, here (the list objects are kept)
             for i in range(len(net)):
@@ -397,9 +397,9 @@ class BasicMultiUpdateBlock(_Planned):
             corr, disp = _f32(corr), _f32(disp)
         for t in (*net, *(t for level in inp for t in level), disp):
             if isinstance(t, torch.Tensor):
-                _check(t, "update block input")
+                _lib.check_f32(t, "update block input")
         if isinstance(corr, torch.Tensor):
-            _check(corr, "corr")
+            _lib.check_f32(corr, "corr")
         if iter16:
             net[2] = self.gru16(net[2], *(inp[2]), pool2x(net[1]))
         if iter08:

@@ -6,7 +6,10 @@ dW, dx and db against float64 `F.conv_transpose2d` autograd on the CPU.  Bar per
 with err32 the error of the same torch expression run in float32 on the CPU, computed here.  Channel pairs: (32, 32)
 `spx_2_gru.conv1`, (64, 9) `spx_gru` (three blocks of three output channels, four N tiles), (8, 3) one partly filled N
 tile and one block of three waves.  Planes 1 x 3 (a single brick, every tap row meets a border), 5 x 7 (odd, under one
-brick wide), 8 x 16 (two bricks); batch 1 and 3 (bricks of several batch items in one split sequence).
+brick wide), 8 x 16 (two bricks), 13 x 3 (four bricks per item: the smallest plane of that width whose split count at batch
+3 is at least 5 and no multiple of 4); batch 1 and 3 (bricks of several batch items in one split sequence).  Split counts
+(the workspace size over numel(dW)): 1 or 3 on the first three planes, and on 13 x 3 two at batch 1 (two of the four quarters of the split
+sum are empty) and six at batch 3 (quarters of 1, 2, 1 and 2 splits).
 
 Measured on the MI355X: at most 2.4e-7 over out / dx / dW / db of all cases (bars 1.1e-6 to 3.0e-6)."""
 import pytest
@@ -19,7 +22,7 @@ from diffuvolume_amd.synth import _gen
 
 pytestmark = pytest.mark.gpu
 CHANNELS = [(32, 32), (64, 9), (8, 3)]
-PLANES = [(1, 3), (5, 7), (8, 16)]
+PLANES = [(1, 3), (5, 7), (8, 16), (13, 3)]
 
 
 def inputs(cin, cout, h, w, b):

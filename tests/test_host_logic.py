@@ -192,6 +192,22 @@ def test_rendezvous_port_below_the_ephemeral_range():
         sk.bind(("127.0.0.1", next(iter(ports))))          # still free
 
 
+def test_training_functions_refuse_a_non_tensor(monkeypatch):
+    """train3d, train2d and train_tail share the tensor check of the later routes (_lib.check_f32): something that is not
+    a tensor is a TypeError that names the argument, not an AttributeError from inside the check."""
+    from diffuvolume_amd import train2d, train3d, train_tail
+    for k in ("DV_TRAIN_CONV3D", "DV_TRAIN_CONV2D", "DV_TRAIN_TAIL"):
+        monkeypatch.delenv(k, raising=False)
+    w3, w2 = torch.zeros(2, 2, 3, 3, 3), torch.zeros(2, 2, 3, 3)
+    calls = [lambda: train3d.conv3d([1.0], w3), lambda: train3d.conv_transpose3d([1.0], w3),
+             lambda: train3d.feature_gate_train([1.0], w2), lambda: train2d.conv2d([1.0], w2),
+             lambda: train2d.deconv2d_k4_weight_grad([1.0], w2), lambda: train2d.conv2d_s2([1.0], w2),
+             lambda: train_tail.upsample_softmax_regress_train([1.0])]
+    for call in calls:
+        with pytest.raises(TypeError, match="must be a tensor"):
+            call()
+
+
 def test_one_place_for_switches(monkeypatch):
     """The native library reads no environment variable (kernel choices are pinned through dv_*_set_* hooks), and every
     DV_* variable the Python side reads is listed in diffuvolume_amd/_env.py -- the list bench.py reports overrides from."""
@@ -206,6 +222,13 @@ def test_one_place_for_switches(monkeypatch):
         read |= set(re.findall(r"environ(?:\.get|\.setdefault)?\(\s*[\"'](DV_[A-Z0-9_]+)[\"']", f.read_text()))
         read |= set(re.findall(r"environ\[\s*[\"'](DV_[A-Z0-9_]+)[\"']\s*\]", f.read_text()))
     assert read <= set(_env.KNOBS), read - set(_env.KNOBS)
+    # the training route switches are read in one place, _env.route(knob): no other file of the package has an `environ`
+    # expression that names one, and a knob that is not a row of KNOBS is refused
+    for f in (root / "diffuvolume_amd").glob("*.py"):
+        if f.name != "_env.py":
+            assert not re.search(r"\benviron\b[^\n]*DV_TRAIN_", f.read_text()), f.name
+    with pytest.raises(KeyError):
+        _env.route("DV_TRAIN_NO_SUCH_ROUTE")
     for k in _env.KNOBS:
         monkeypatch.delenv(k, raising=False)
     assert _env.overrides() == {}

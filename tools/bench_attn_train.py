@@ -39,13 +39,14 @@ HBM = 8.0e12
 PEAK = 157.3e12                                         # fp32 MFMA peak of the MI355X
 PARTS = ("function", "kernels", "acv")
 SHAPE = (128, 12, 16, 32)                               # (C, D, H, W): the bottleneck of a 256 x 512 pair
-# -Rpass-analysis=kernel-resource-usage of csrc/window_attn_bwd.hip (hipcc, gfx950, the flags of _build.py).
+# -Rpass-analysis=kernel-resource-usage of csrc/window_attn_bwd.hip and, for the split sum, csrc/splitk_reduce.hip (hipcc,
+# gfx950, the flags of _build.py).
 RESOURCES = {
     "window_attn_bwd_kernel (256 threads, one block per window)": dict(
         vgprs=255, agprs=52, vgpr_spills=0, sgpr_spills=0, scratch_bytes=0, lds_bytes=106112, waves_per_simd=1),
     "attn_wgrad_kernel (256 threads, 128 x 128 tile of one split)": dict(vgprs=151, agprs=0, vgpr_spills=0, sgpr_spills=0,
                                                                          scratch_bytes=0, lds_bytes=34816, waves_per_simd=3),
-    "attn_wgrad_sum_kernel": dict(vgprs=6, vgpr_spills=0, sgpr_spills=0, scratch_bytes=0, lds_bytes=0, waves_per_simd=8),
+    "splitk_sum_kernel": dict(vgprs=8, vgpr_spills=0, sgpr_spills=0, scratch_bytes=0, lds_bytes=0, waves_per_simd=8),
     "attn_bwd_bias_kernel (one wave per feature)": dict(vgprs=10, vgpr_spills=0, sgpr_spills=0, scratch_bytes=0, lds_bytes=0,
                                                         waves_per_simd=8),
     "attn_bwd_dbp_kernel (256 threads, one block per channel)": dict(vgprs=12, vgpr_spills=0, sgpr_spills=0, scratch_bytes=0,
