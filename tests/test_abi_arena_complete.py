@@ -1,6 +1,7 @@
 """Every export of the C ABI is either a row of the arena table (tests/test_gpu_abi_arena.py) or excluded here for a stated
 reason, so that a new entry point cannot arrive without a decision about its pointer and bounds contract."""
 from diffuvolume_amd import _lib
+import test_gpu_abi_arena as T
 from test_gpu_abi_arena import TABLE
 
 SIZE_OR_CHOICE = "only returns a size, a version, a string or a choice: launches nothing"
@@ -11,11 +12,6 @@ HOOK = "process-wide test hook: launches nothing"
 def TRAINED(test):
     return f"training entry whose misaligned-view test already exists: {test}"
 
-
-# Weight-gradient entries of the training route.  Their host entries neither branch on nor refuse by the alignment of a
-# tensor operand (csrc/*wgrad*.hip, deconv*_k4_bwd.hip: only the 16-byte `workspace` of the 2-D k4 form is checked), so an
-# offset view selects no other code; they are outside this table of inference entries and have no offset-view test yet.
-WGRAD = "training weight-gradient entry: no alignment predicate on a tensor operand, outside the inference table"
 
 EXCLUDED = {
     "dv_version": SIZE_OR_CHOICE,
@@ -73,14 +69,6 @@ EXCLUDED = {
     "dv_gru_gates_bwd_reset_f32": TRAINED("test_gpu_update_train.py::test_gate_kernels_tails_and_misaligned_views"),
     "dv_gru_reset_mul_f16": TRAINED("test_gpu_conv2d_wgrad_cat_f16.py::test_gate_kernels_match_torch_half_arithmetic"),
     "dv_gru_blend_f16": TRAINED("test_gpu_conv2d_wgrad_cat_f16.py::test_gate_kernels_match_torch_half_arithmetic"),
-    "dv_conv3d_wgrad_f32": WGRAD,
-    "dv_deconv3d_k4s2_wgrad_f32": WGRAD,
-    "dv_conv2d_wgrad_f32": WGRAD,
-    "dv_conv2d_wgrad_cat_f32": WGRAD,
-    "dv_conv2d_wgrad_cat_f16": WGRAD,
-    "dv_conv2d_1in_wgrad_f32": WGRAD,
-    "dv_deconv2d_k4s2_wgrad_f32": WGRAD,
-    "dv_conv2d_fewin_wgrad_f32": WGRAD,
 }
 
 
@@ -95,6 +83,34 @@ def test_every_export_is_a_row_or_an_exclusion():
     assert not missing, ("exports with no decision: add a row to tests/test_gpu_abi_arena.py or an exclusion with its reason "
                          f"here: {sorted(missing)}")
     assert all(isinstance(v, str) and len(v) > 20 for v in EXCLUDED.values())
+
+
+def test_no_weight_gradient_entry_is_excluded():
+    assert not [n for n in EXCLUDED if "wgrad" in n and not n.endswith("_workspace_floats")]
+    assert {n for n in _lib.SIGNATURES if "wgrad" in n and not n.endswith("_workspace_floats")} == set(T.WGRAD_REQUIRED)
+
+
+def test_weight_gradient_rows_meet_their_shape_conditions():
+    """The rows of a weight-gradient entry are there for stated shape conditions (channel tails, a second channel tile,
+    plane tails, one split, a ragged split range, ...): every builder holds its own from the size entry -- which needs no
+    GPU, so the rows are built here -- and between them the rows of an entry state all the entry asks for.  The pairs a
+    row declares bit-equal must be placements the harness really runs and accepts."""
+    from diffuvolume_amd import _build
+    _build.build()
+    met = {entry: set() for entry in T.WGRAD_REQUIRED}
+    for r in TABLE:
+        if r.entry not in T.WGRAD_REQUIRED:
+            continue
+        case = r.build()                                   # asserts r.build.claims
+        met[r.entry] |= set(r.build.claims)
+        assert set(case.outs) == ({"dw"} if r.entry == "dv_conv2d_1in_wgrad_f32" else {"dw", "workspace"}), r.name
+        assert set(case.ref) == {"dw"} and not case.inout, r.name
+        accepted = {label for label, _, want in T.variants_of(r, case) if want == T.OK}
+        refused = {label for label, _, want in T.variants_of(r, case) if want != T.OK}
+        assert accepted - {"a"} == {y for x, y in r.same_bits if x == "a"}, (r.name, sorted(accepted))
+        assert bool(refused) == bool(r.refuse), r.name
+    for entry, need in T.WGRAD_REQUIRED.items():
+        assert need <= met[entry], (entry, sorted(need - met[entry]))
 
 
 def test_the_named_tests_exist():

@@ -1,6 +1,9 @@
 """The pointer and bounds contract of the C ABI (include/diffuvolume_hip.h), entry point by entry point.
 
-Every inference entry that launches a kernel and writes a caller-owned tensor is a row of ``TABLE``.  A row builds its
+Every inference entry that launches a kernel and writes a caller-owned tensor is a row of ``TABLE``, and so are the training
+entries that choose a path or refuse by alignment and the eight split-K weight-gradient entries, whose ``workspace`` is an
+output operand of exactly the size their ``*_workspace_floats`` entry reports: every word of it written, none next to it
+(the other training entries name their own offset-view test in tests/test_abi_arena_complete.py).  A row builds its
 operands on the CPU, states the float64 reference as the existing test of that entry states it, and copies that test's
 bar (``cite`` names the test).  Each row then runs, with EVERY operand inside a guard-banded arena (tests/arena.py):
 
@@ -1039,6 +1042,192 @@ def _context_upsample_bwd(shape, softmax):
     return build
 
 
+# ------------------------------------------------------------------ rows: the split-K weight gradients of the training routes
+# `workspace` is an OUTPUT of exactly *_workspace_floats(...) floats: the first kernel must write every word of it (the split
+# sum reads them all back) and none next to it (production allocates exactly that many).  References and bars are those of
+# the entries' own tests; a row's `claims` are the shape conditions it is there for, held from the size entry when it is built.
+WGRAD_REQUIRED = {  # entry -> the conditions its rows must meet between them (tests/test_abi_arena_complete.py)
+    "dv_conv3d_wgrad_f32": {"channel_tails", "channel_tiles", "plane_tails", "one_split", "ragged_splits"},
+    "dv_deconv3d_k4s2_wgrad_f32": {"channel_tails", "plane_tails", "one_split", "ragged_splits"},
+    "dv_conv2d_wgrad_f32": {"channel_tails", "channel_tiles", "plane_tails", "one_split", "ragged_splits"},
+    "dv_conv2d_wgrad_cat_f32": {"channel_tails", "plane_tails", "one_split", "ragged_splits", "source_boundary", "k1", "k3"},
+    "dv_conv2d_wgrad_cat_f16": {"channel_tails", "plane_tails", "one_split", "ragged_splits", "source_boundary", "k1", "k3"},
+    "dv_conv2d_1in_wgrad_f32": {"channel_tails", "plane_tails"},       # no workspace, no splits: one block per (co, ky)
+    "dv_deconv2d_k4s2_wgrad_f32": {"channel_tails", "plane_tails", "one_split", "ragged_splits"},
+    "dv_conv2d_fewin_wgrad_f32": {"channel_tails", "plane_tails", "one_split", "ragged_splits"},
+}
+U24 = 2.0 ** -24
+
+
+def wg_assert(claims, cout, cin, plane, brick, nbricks=1, splits=1, tile=0, bounds=(), k=0):
+    """plane: the extents the bricks tile; tile: the block's channel tile where a second one is asked for; bounds: the first
+    channels of the later sources of a concatenation."""
+    facts = {
+        "channel_tails": cout % 16 != 0 and cin % 16 != 0,
+        "channel_tiles": tile > 0 and (cout > tile or cin > tile),
+        "plane_tails": all(n % t != 0 for n, t in zip(plane, brick)),
+        "one_split": splits == 1,
+        "ragged_splits": splits >= 3 and nbricks % splits != 0,
+        "source_boundary": any(o % 16 != 0 for o in bounds),
+        "k1": k == 1,
+        "k3": k == 3,
+    }
+    for c in claims:
+        assert facts[c], f"the row no longer is a case of {c}: Cout {cout}, Cin {cin}, plane {tuple(plane)} in bricks of {brick}, " \
+                         f"{nbricks} bricks over {splits} splits"
+
+
+def bar_wgrad(mag, c):
+    """Per element |dW - dW_f64| <= c * 2^-24 * sum |g x|: `mag` is that sum, c the depth_c / wgrad_c of the cited test."""
+    def check(name, got, ref):
+        err = (got.double() - ref).abs()
+        print(f"    {name}: worst err / (u * mag) = {float((err / (mag * U24).clamp(min=1e-300)).max()):.1f} (c = {c})")
+        assert torch.all(err <= c * U24 * mag), (name, c)
+    return check
+
+
+def wg_same_bits(operands, refused=()):
+    """Variant (a) against every accepted displaced variant of a row without predicate operands: the sources promise that
+    the bits depend on the shape only, so a path chosen by alignment would show here (labels as variants_of makes them)."""
+    moved = [f"o:{n}" for n in operands if n not in refused]
+    return tuple(("a", v) for v in moved + [f"c{k}" + ("-accepted" if refused else "") for k in (1, 2, 3)])
+
+
+def _wg_conv3d(cin, cout, k, stride, b, dims, claims, seed=401):
+    def build():
+        from test_gpu_conv3d_wgrad import BRICK, depth_c, out_dims, ref_wgrad, split_plan
+        gen = G(seed)
+        out = out_dims(dims, k, stride)
+        x, g = torch.randn(b, cin, *dims, generator=gen), torch.randn(b, cout, *out, generator=gen)
+        nbricks, splits, _ = split_plan(b, cin, dims, cout, k, stride)
+        wg_assert(claims, cout, cin, out, BRICK[(k, stride)], nbricks, splits, tile=32)
+        nws = _lib.load().dv_conv3d_wgrad_workspace_floats(b, cin, *dims, cout, k, stride)
+        assert nws == splits * cout * cin * k ** 3
+        x64, g64 = x.double(), g.double()
+        return Case({"x": x, "g": g}, {"dw": torch.empty(cout, cin, k, k, k), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: lib.dv_conv3d_wgrad_f32(p("x"), p("g"), p("dw"), p("workspace"), b, cin, *dims, cout, k, stride, s),
+                    {"dw": ref_wgrad(x64, g64, k, stride)},
+                    bar_wgrad(ref_wgrad(x64.abs(), g64.abs(), k, stride), depth_c(b, cin, dims, cout, k, stride)))
+    build.claims = claims
+    return build
+
+
+def _wg_deconv3d_k4(ci, co, b, dims, claims, seed=402):
+    def build():
+        from test_gpu_deconv3d_k4_bwd import BRICK, f64_backward, split_plan, wgrad_c
+        gen = G(seed)
+        x, g = torch.randn(b, ci, *dims, generator=gen), torch.randn(b, co, *[2 * n for n in dims], generator=gen)
+        nbricks, splits, _ = split_plan(ci, co, b, dims)
+        wg_assert(claims, co, ci, dims, BRICK, nbricks, splits)
+        nws = _lib.load().dv_deconv3d_k4s2_wgrad_workspace_floats(b, ci, *dims, co)
+        assert nws == splits * ci * co * 64
+        w0 = torch.zeros(ci, co, 4, 4, 4)                 # dW does not depend on the weights
+        return Case({"x": x, "g": g}, {"dw": torch.empty(ci, co, 4, 4, 4), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: lib.dv_deconv3d_k4s2_wgrad_f32(p("x"), p("g"), p("dw"), p("workspace"), b, ci, *dims, co, s),
+                    {"dw": f64_backward(x, w0, g)[1]}, bar_wgrad(f64_backward(x.abs(), w0, g.abs())[1], wgrad_c(ci, co, b, dims)))
+    build.claims = claims
+    return build
+
+
+def _wg_conv2d(cin, cout, k, dil, b, h, w, claims, seed=403):
+    def build():
+        from test_gpu_conv2d_wgrad import brick, depth_c, ref_wgrad
+        gen = G(seed)
+        x, g = torch.randn(b, cin, h, w, generator=gen), torch.randn(b, cout, h, w, generator=gen)
+        nws = _lib.load().dv_conv2d_wgrad_workspace_floats(b, cin, h, w, cout, k, dil)
+        ty, tx = brick(k, dil)
+        nbricks, splits = b * -(-h // ty) * -(-w // tx), nws // (cout * cin * k * k)
+        assert nws > 0 and nws == splits * cout * cin * k * k
+        wg_assert(claims, cout, cin, (h, w), (ty, tx), nbricks, splits, tile=32)
+        x64, g64 = x.double(), g.double()
+        return Case({"x": x, "g": g}, {"dw": torch.empty(cout, cin, k, k), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: lib.dv_conv2d_wgrad_f32(p("x"), p("g"), p("dw"), p("workspace"), b, cin, h, w, cout, k, dil, s),
+                    {"dw": ref_wgrad(x64, g64, k, dil)}, bar_wgrad(ref_wgrad(x64.abs(), g64.abs(), k, dil), depth_c(b, cin, h, w, cout, k, dil)))
+    build.claims = claims
+    return build
+
+
+def _wg_conv2d_cat(f16, chans, cout, k, b, h, w, claims, seed=404):
+    def build():
+        from test_gpu_conv2d_wgrad_cat import ref_wgrad
+        if f16:          # the contract of the fp16 entry: the float64 gradient of the operands rounded to fp16
+            from test_gpu_conv2d_wgrad_cat_f16 import TX, TY, depth_c, splits_of
+            rnd, entry = (lambda t: t.half().double()), "dv_conv2d_wgrad_cat_f16"
+        else:
+            from test_gpu_conv2d_wgrad_cat import TX, TY, depth_c, splits_of
+            rnd, entry = (lambda t: t.double()), "dv_conv2d_wgrad_cat_f32"
+        gen = G(seed)
+        cin = sum(chans)
+        xs = [torch.randn(b, c, h, w, generator=gen) for c in chans]
+        g = torch.randn(b, cout, h, w, generator=gen)
+        splits = splits_of(chans, b, h, w, cout, k)                        # the size entry over numel(dW), checked to be whole
+        nws = splits * cout * cin * k * k
+        bounds = [sum(chans[:i]) for i in range(1, len(chans))]
+        wg_assert(claims, cout, cin, (h, w), (TY, TX), b * -(-h // TY) * -(-w // TX), splits, bounds=bounds, k=k)
+        names = [f"in{i}" for i in range(len(xs))]
+        x64, g64 = torch.cat([rnd(t) for t in xs], dim=1), rnd(g)
+        inputs = dict(zip(names, xs))
+        inputs["g"] = g
+        return Case(inputs, {"dw": torch.empty(cout, cin, k, k), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: getattr(lib, entry)(ptr_array(p, names), int_array(list(chans)), len(names), p("g"), p("dw"),
+                                                          p("workspace"), b, h, w, cout, k, s),
+                    {"dw": ref_wgrad(x64, g64, k)}, bar_wgrad(ref_wgrad(x64.abs(), g64.abs(), k), depth_c(chans, b, h, w, cout, k)))
+    build.claims = claims
+    return build
+
+
+def _wg_conv2d_1in(cout, b, h, w, claims, seed=405):
+    def build():
+        k = 7
+        gen = G(seed)
+        x, g = torch.randn(b, 1, h, w, generator=gen), torch.randn(b, cout, h, w, generator=gen)
+        wg_assert(claims, cout, 1, (b * h * w,), (256,))            # no bricks: the 256 threads stride over all B H W positions
+        ref = torch.nn.grad.conv2d_weight(x.double(), (cout, 1, k, k), g.double(), padding=k // 2)
+        mag = torch.nn.grad.conv2d_weight(x.double().abs(), (cout, 1, k, k), g.double().abs(), padding=k // 2)
+        return Case({"x": x, "g": g}, {"dw": torch.empty(cout, 1, k, k)},
+                    lambda lib, p, s: lib.dv_conv2d_1in_wgrad_f32(p("x"), p("g"), p("dw"), b, h, w, cout, k, s),
+                    {"dw": ref}, bar_wgrad(mag, -(-b * h * w // 256) + 8))        # a chain of ceil(BHW / 256), then an 8-level tree
+    build.claims = claims
+    return build
+
+
+def _wg_deconv2d_k4(ci, co, b, h, w, claims):
+    """Bar of test_gradients_match_float64_autograd ("dw"): relative L2 <= 2 x that of float32 torch + 1e-6."""
+    def build():
+        from test_gpu_deconv2d_k4_bwd import inputs as k4_inputs, torch_grads
+        x, wt, bias, cot = k4_inputs(ci, co, h, w, b)
+        nws = _lib.load().dv_deconv2d_k4s2_wgrad_workspace_floats(b, ci, h, w, co)
+        nbricks, splits = b * -(-h // 4) * -(-w // 16), nws // (ci * co * 16)        # bricks of 4 x 16 pixels of x
+        assert nws > 0 and nws == splits * ci * co * 16
+        wg_assert(claims, co, ci, (h, w), (4, 16), nbricks, splits)
+        r64, r32 = torch_grads(x, wt, bias, cot, torch.float64)["dw"], torch_grads(x, wt, bias, cot, torch.float32)["dw"]
+        return Case({"x": x, "g": cot}, {"dw": torch.empty(ci, co, 4, 4), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: lib.dv_deconv2d_k4s2_wgrad_f32(p("x"), p("g"), p("dw"), p("workspace"), b, ci, h, w, co, s),
+                    {"dw": r64}, _rel_l2_bar({"dw": r32}, {"dw": r64}))
+    build.claims = claims
+    return build
+
+
+def _wg_fewin(cin, k, stride, cout, b, h, w, claims):
+    """Bar of test_fewin_weight_gradient ("dw"): relative L2 <= 2 x that of float32 torch + 1e-6."""
+    def build():
+        from test_gpu_igev_front_bwd import conv_inputs, conv_torch
+        x, wt, bias, cot = conv_inputs(cin, cout, k, stride, h, w, b, 62)
+        ho, wo = cot.shape[2:]
+        nws = _lib.load().dv_conv2d_fewin_wgrad_workspace_floats(b, cin, h, w, cout, k, stride)
+        nbricks, splits = b * -(-ho // 8) * -(-wo // 16), nws // (cout * cin * k * k)  # bricks of 8 x 16 output pixels
+        assert nws > 0 and nws == splits * cout * cin * k * k
+        wg_assert(claims, cout, cin, (ho, wo), (8, 16), nbricks, splits)
+        r64 = conv_torch(x, wt, bias, cot, stride, torch.float64, False)["dw"]
+        r32 = conv_torch(x, wt, bias, cot, stride, torch.float32, False)["dw"]
+        return Case({"x": x, "g": cot}, {"dw": torch.empty(cout, cin, k, k), "workspace": torch.empty(nws)},
+                    lambda lib, p, s: lib.dv_conv2d_fewin_wgrad_f32(p("x"), p("g"), p("dw"), p("workspace"), b, cin, h, w, cout, k,
+                                                                    stride, s),
+                    {"dw": r64}, _rel_l2_bar({"dw": r32}, {"dw": r64}))
+    build.claims = claims
+    return build
+
+
 # ------------------------------------------------------------------ the table
 WP = {"wpacked": (ERR_ALIGN, 16)}
 R = Row
@@ -1274,6 +1463,83 @@ TABLE = [
       pred=("x", "g", "dx")),
     R("context_upsample_bwd", "dv_context_upsample_bwd_f32", _context_upsample_bwd((2, 5, 7), True), "test_gradients_match_float64_autograd",
       variants="ac", refuse={"weights": (ERR_ALIGN, 16), "grad_out": (ERR_ALIGN, 16), "d_weights": (ERR_ALIGN, 16)}),
+]
+
+
+def WG(name, entry, build, cite, operands=("x", "g", "dw", "workspace"), refuse=None):
+    """A weight-gradient row: no alignment predicate, so every operand is displaced alone as an "other" one, and every
+    accepted placement must give the bits of the aligned one."""
+    return Row(name, entry, build, cite, refuse=refuse, same_bits=wg_same_bits(operands, refused=tuple(refuse or ())))
+
+
+CAT3, CAT2 = ("in0", "in1", "in2", "g", "dw", "workspace"), ("in0", "in1", "g", "dw", "workspace")
+TABLE += [
+    # 3-D convolutions: k3 s1, k3 s2, k1; one brick; 36 bricks over 32 splits of 4 x 4 channel tiles
+    WG("wgrad3d_k3s1", "dv_conv3d_wgrad_f32", _wg_conv3d(20, 40, 3, 1, 2, (3, 5, 18), ("channel_tails", "channel_tiles", "plane_tails")),
+       "test_conv_weight_gradient"),
+    WG("wgrad3d_k3s2", "dv_conv3d_wgrad_f32", _wg_conv3d(5, 33, 3, 2, 1, (5, 9, 19), ("channel_tails", "channel_tiles", "plane_tails")),
+       "test_conv_weight_gradient"),
+    WG("wgrad3d_k1", "dv_conv3d_wgrad_f32", _wg_conv3d(33, 17, 1, 1, 1, (3, 5, 17), ("channel_tails", "channel_tiles", "plane_tails")),
+       "test_conv_weight_gradient"),
+    WG("wgrad3d_one_brick", "dv_conv3d_wgrad_f32", _wg_conv3d(5, 7, 3, 1, 1, (2, 3, 9), ("channel_tails", "one_split")),
+       "test_conv_weight_gradient"),
+    WG("wgrad3d_ragged_splits", "dv_conv3d_wgrad_f32", _wg_conv3d(100, 100, 1, 1, 3, (5, 5, 17),
+                                                                 ("channel_tails", "channel_tiles", "plane_tails", "ragged_splits")),
+       "test_conv_weight_gradient"),
+    # k4 transposed 3-D: two K waves share a brick; the three-tile block on one brick; 144 bricks over 128 splits
+    WG("wgrad3d_k4", "dv_deconv3d_k4s2_wgrad_f32", _wg_deconv3d_k4(20, 9, 2, (3, 5, 9), ("channel_tails", "plane_tails")),
+       "test_weight_gradient"),
+    WG("wgrad3d_k4_three_tiles", "dv_deconv3d_k4s2_wgrad_f32", _wg_deconv3d_k4(48, 32, 1, (2, 3, 5), ("one_split",)), "test_weight_gradient"),
+    WG("wgrad3d_k4_ragged_splits", "dv_deconv3d_k4s2_wgrad_f32", _wg_deconv3d_k4(20, 9, 3, (7, 15, 20),
+                                                                                ("channel_tails", "plane_tails", "ragged_splits")),
+       "test_weight_gradient"),
+    # dilated 2-D: 4 x 32 bricks, the 2 x 32 bricks of dilation > 4, k1; one brick; 36 bricks over 32 splits
+    WG("wgrad2d_k3", "dv_conv2d_wgrad_f32", _wg_conv2d(20, 40, 3, 1, 2, 9, 33, ("channel_tails", "channel_tiles", "plane_tails")),
+       "test_weight_gradient"),
+    WG("wgrad2d_k3_d5", "dv_conv2d_wgrad_f32", _wg_conv2d(5, 7, 3, 5, 1, 7, 37, ("channel_tails", "plane_tails")), "test_weight_gradient"),
+    WG("wgrad2d_k1", "dv_conv2d_wgrad_f32", _wg_conv2d(33, 17, 1, 1, 1, 5, 35, ("channel_tails", "channel_tiles", "plane_tails")),
+       "test_weight_gradient"),
+    WG("wgrad2d_one_brick", "dv_conv2d_wgrad_f32", _wg_conv2d(5, 7, 3, 1, 1, 3, 20, ("channel_tails", "one_split")), "test_weight_gradient"),
+    WG("wgrad2d_ragged_splits", "dv_conv2d_wgrad_f32", _wg_conv2d(100, 100, 1, 1, 3, 21, 33,
+                                                                 ("channel_tails", "channel_tiles", "plane_tails", "ragged_splits")),
+       "test_weight_gradient"),
+    # over a virtual concatenation, fp32 and fp16 operands: source boundaries at channels 20 and 26 of two 64-wide tiles
+    WG("wgrad_cat_k3", "dv_conv2d_wgrad_cat_f32", _wg_conv2d_cat(False, (20, 6, 39), 33, 3, 2, 5, 33,
+                                                                 ("channel_tails", "plane_tails", "source_boundary", "k3")),
+       "test_edge_shapes", operands=CAT3),
+    WG("wgrad_cat_k1_ragged_splits", "dv_conv2d_wgrad_cat_f32", _wg_conv2d_cat(False, (5, 13, 3), 7, 1, 3, 9, 65,
+                                                                               ("channel_tails", "plane_tails", "source_boundary", "k1",
+                                                                                "ragged_splits")),
+       "test_edge_shapes", operands=CAT3),
+    WG("wgrad_cat_one_split", "dv_conv2d_wgrad_cat_f32", _wg_conv2d_cat(False, (5, 3), 7, 3, 1, 3, 20, ("channel_tails", "one_split", "k3")),
+       "test_edge_shapes", operands=CAT2),
+    WG("wgrad_cat_f16_k3", "dv_conv2d_wgrad_cat_f16", _wg_conv2d_cat(True, (20, 6, 39), 33, 3, 2, 5, 33,
+                                                                     ("channel_tails", "plane_tails", "source_boundary", "k3")),
+       "test_edge_shapes", operands=CAT3),
+    WG("wgrad_cat_f16_k1_ragged_splits", "dv_conv2d_wgrad_cat_f16", _wg_conv2d_cat(True, (5, 13, 3), 7, 1, 3, 9, 65,
+                                                                                   ("channel_tails", "plane_tails", "source_boundary",
+                                                                                    "k1", "ragged_splits")),
+       "test_edge_shapes", operands=CAT3),
+    WG("wgrad_cat_f16_one_split", "dv_conv2d_wgrad_cat_f16", _wg_conv2d_cat(True, (5, 3), 7, 3, 1, 3, 20,
+                                                                            ("channel_tails", "one_split", "k3")),
+       "test_edge_shapes", operands=CAT2),
+    WG("wgrad_1in", "dv_conv2d_1in_wgrad_f32", _wg_conv2d_1in(5, 3, 9, 33, ("channel_tails", "plane_tails")),
+       "test_single_input_channel_weight_gradient", operands=("x", "g", "dw")),
+    # k4 transposed 2-D: float4 stores into the workspace, so a workspace off a 16-byte boundary is refused and nothing runs
+    WG("wgrad2d_k4", "dv_deconv2d_k4s2_wgrad_f32", _wg_deconv2d_k4(20, 9, 2, 5, 17, ("channel_tails", "plane_tails")),
+       "test_gradients_match_float64_autograd", refuse={"workspace": (ERR_ALIGN, 16)}),
+    WG("wgrad2d_k4_ragged_splits", "dv_deconv2d_k4s2_wgrad_f32", _wg_deconv2d_k4(32, 32, 3, 9, 3, ("plane_tails", "ragged_splits")),
+       "test_gradients_match_float64_autograd", refuse={"workspace": (ERR_ALIGN, 16)}),
+    WG("wgrad2d_k4_one_split", "dv_deconv2d_k4s2_wgrad_f32", _wg_deconv2d_k4(8, 3, 1, 5, 7, ("channel_tails", "plane_tails", "one_split")),
+       "test_gradients_match_float64_autograd", refuse={"workspace": (ERR_ALIGN, 16)}),
+    # few input channels: the 7 x 7 stride-2 stem, k3 over 9 bricks in 4 splits, k5 on one brick
+    WG("wgrad_fewin_stem", "dv_conv2d_fewin_wgrad_f32", _wg_fewin(3, 7, 2, 20, 2, 17, 33, ("channel_tails", "plane_tails")),
+       "test_fewin_weight_gradient"),
+    WG("wgrad_fewin_k3_ragged_splits", "dv_conv2d_fewin_wgrad_f32", _wg_fewin(4, 3, 1, 5, 1, 17, 33,
+                                                                             ("channel_tails", "plane_tails", "ragged_splits")),
+       "test_fewin_weight_gradient"),
+    WG("wgrad_fewin_k5_one_split", "dv_conv2d_fewin_wgrad_f32", _wg_fewin(1, 5, 2, 5, 1, 9, 20, ("channel_tails", "plane_tails", "one_split")),
+       "test_fewin_weight_gradient"),
 ]
 assert len({r.name for r in TABLE}) == len(TABLE)
 

@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from diffuvolume_amd import _lib, train3d
+from test_gpu_conv3d_wgrad import assert_long_splits, split_ranges
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -29,6 +30,14 @@ SHAPES = [  # (Ci, Co, B, dims of x)
     (32, 16, 1, (3, 4, 7)),         # odd W: scalar path
     (48, 32, 3, (2, 3, 5)),         # 48 is no tile multiple; three batch items over the K split
     (16, 8, 1, (1, 1, 1)),          # every tap is border
+]
+# The split count is min(2048 / waves of the channel tiles, 48 MB / numel(dW), bricks): in SHAPES every split is one brick.
+# These have more bricks than splits, so that a block walks two bricks and, in one split, bricks of two batch items
+# (assert_long_splits; tests/test_wgrad_split_cases_host.py holds the same without a GPU), on every wave layout.
+LONG = [  # (Ci, Co, B, dims of x)
+    (64, 64, 3, (5, 9, 9)),         # 2 x 2 tiles, one K wave: 54 bricks over 32 splits, a tail in every brick dimension
+    (32, 16, 3, (8, 16, 32)),       # 2 x 1 tiles, two K waves: 192 bricks over 128 splits
+    (16, 8, 3, (8, 16, 32)),        # one tile, four K waves: the accumulators pass through the tiles' LDS after two bricks
 ]
 
 
@@ -43,10 +52,16 @@ def k_waves(ci, co):
     return 1 if tiles >= 4 else 4 // tiles
 
 
-def wgrad_c(ci, co, b, dims):
-    nbricks = b * math.prod(-(-n // t) for n, t in zip(dims, BRICK))
+def split_plan(ci, co, b, dims):
+    """(bricks, splits, bricks of one batch item): the bricks from the kernel's brick, the splits from the size entry."""
+    per_item = math.prod(-(-n // t) for n, t in zip(dims, BRICK))
     splits = _lib.load().dv_deconv3d_k4s2_wgrad_workspace_floats(b, ci, *dims, co) // (ci * co * 64)
     assert splits >= 1
+    return b * per_item, splits, per_item
+
+
+def wgrad_c(ci, co, b, dims):
+    nbricks, splits, _ = split_plan(ci, co, b, dims)
     kw = k_waves(ci, co)
     return -(-nbricks // splits) * math.prod(BRICK) // kw + (kw - 1) + splits
 
@@ -86,6 +101,24 @@ def test_weight_gradient(ci, co, b, dims):
     assert torch.all(err <= c * U * mw)
 
 
+@pytest.mark.parametrize("ci,co,b,dims", LONG)
+def test_weight_gradient_long_splits(ci, co, b, dims):
+    """A block walks several bricks: the barrier before the re-staging, the overwrite of the LDS tiles, the brick index
+    taken apart across y, z and batch boundaries inside one split, the accumulation over the bricks, and for KW > 1 the
+    hand-over of the K waves' accumulators through the LDS of the tiles after the last brick."""
+    nbricks, splits, per_item = split_plan(ci, co, b, dims)
+    straddling = assert_long_splits(nbricks, splits, per_item)
+    x, w, g, _, dw, _, mw = case(ci, co, b, dims)
+    out = train3d.deconv3d_k4_weight_grad(x.cuda(), g.cuda()).cpu().double()
+    c = wgrad_c(ci, co, b, dims)
+    err = (out - dw).abs()
+    sizes = sorted({b1 - b0 for b0, b1 in split_ranges(nbricks, splits)})
+    print(f"LONG k4 wgrad {ci}->{co} B{b} {dims}: K waves {k_waves(ci, co)}, nbricks {nbricks}, splits {splits}, bricks per split "
+          f"{sizes}, two batch items in splits {straddling}, worst err / (u * mag) = "
+          f"{float((err / (mw * U).clamp(min=1e-300)).max()):.1f}, c = {c}")
+    assert torch.all(err <= c * U * mw)
+
+
 def test_misaligned_pointers_take_the_scalar_path():
     """W % 4 == 0 but g starts 4 bytes off a 16-byte boundary: no error, and the same bits as the vector path."""
     ci, co, b, dims = SHAPES[0]
@@ -103,12 +136,28 @@ def test_two_launches_same_bits():
         x, w, g = (t.cuda() for t in case(ci, co, b, dims)[:3])
         assert torch.equal(train3d.deconv3d_k4_weight_grad(x, g), train3d.deconv3d_k4_weight_grad(x, g))
         assert torch.equal(train3d.deconv3d_k4_input_grad(g, w), train3d.deconv3d_k4_input_grad(g, w))
+    ci, co, b, dims = LONG[2]                                            # several bricks per block, four K waves
+    assert_long_splits(*split_plan(ci, co, b, dims))
+    x, g = case(ci, co, b, dims)[0].cuda(), case(ci, co, b, dims)[2].cuda()
+    assert torch.equal(train3d.deconv3d_k4_weight_grad(x, g), train3d.deconv3d_k4_weight_grad(x, g))
 
 
 def test_nan_stays_in_its_input_channel():
     ci, co, b, dims = SHAPES[2]
     x, _, g = (t.clone() for t in case(ci, co, b, dims)[:3])
     x[1, 37, 1, 2, 3] = float("nan")
+    nan = torch.isnan(train3d.deconv3d_k4_weight_grad(x.cuda(), g.cuda()).cpu())
+    assert nan[37].any() and not nan[:37].any() and not nan[38:].any()
+    # ... and in the SECOND brick of a split (a position of x is read by the one brick that holds it)
+    ci, co, b, dims = LONG[0]
+    nbricks, splits, per_item = split_plan(ci, co, b, dims)
+    assert_long_splits(nbricks, splits, per_item)
+    second = next(b0 for b0, b1 in split_ranges(nbricks, splits) if b1 - b0 >= 2) + 1
+    nb = [-(-n // t) for n, t in zip(dims, BRICK)]
+    item, r = divmod(second, per_item)
+    origin = [i * t for i, t in zip((r // (nb[1] * nb[2]), (r // nb[2]) % nb[1], r % nb[2]), BRICK)]
+    x, g = case(ci, co, b, dims)[0].clone(), case(ci, co, b, dims)[2]
+    x[(item, 37, *origin)] = float("nan")
     nan = torch.isnan(train3d.deconv3d_k4_weight_grad(x.cuda(), g.cuda()).cpu())
     assert nan[37].any() and not nan[:37].any() and not nan[38:].any()
 
