@@ -408,7 +408,10 @@ int dv_disparity_regression_f32(const float* prob, float* disp, int B, int D, in
 int dv_softmax_regress_f32(const float* cost, float* disp, int B, int D, int H, int W, dv_stream_t stream);
 
 /* two-hot encoding of a quarter-resolution disparity (acv_ddim.py:403-419):
- * disp_q [B,h*w] -> x [B,nbins,h*w] = 2*twohot-1. */
+ * disp_q [B,h*w] -> x [B,nbins,h*w] = 2*twohot-1.
+ * disp_q is expected in [0, nbins).  Outside it the reference raises (scatter index out of range); this entry does
+ * not look and writes what its arithmetic gives: every element finite and in [-1,1], all -1 for disp_q >= nbins
+ * (tests/test_gpu_ddim_kernels.py pins that). */
 int dv_encode_two_hot_f32(const float* disp_q, float* x, int B, int nbins, int hw, dv_stream_t stream);
 
 /* One DDIM state update, everything after the regression of one step
@@ -421,7 +424,14 @@ int dv_encode_two_hot_f32(const float* disp_q, float* x, int B, int nbins, int h
  * n01_f32 / n01_f64: exactly one is non-NULL (state dtype of this step).
  * eps_f32 / eps_f64: exactly one non-NULL unless last (randn_like(img) follows img's dtype).
  * disp,unc,used,ens [B,4h,4w]; mask [B,h,w] in/out; fill,x_next,pred_eps fp64 [B,nbins,h,w];
- * pred_eps and ens may be NULL (not wanted). */
+ * pred_eps and ens may be NULL (not wanted).
+ * Rounding points (the reference's dtype promotions, acv_ddim.py:356): x_start * sqrt_alpha_next is a float32
+ * tensor times a 0-dim float64 scalar and is rounded to float32, with sqrt_alpha_next itself rounded to float32
+ * first; sigma * eps_f32 likewise is (float)sigma * eps rounded to float32 (with eps_f64 it is a float64 product);
+ * c * pred_eps, pred_eps itself and the two additions are float64.  x_start and mask are bit-exact statements
+ * (every multiplication on their way is by 0.5 or 2).  x_next and pred_eps are compared with the reference at the
+ * level of float64 ulps and not bit for bit: the library is built with -ffp-contract=on, so a float64 a*b+c may be
+ * one fused operation here and two roundings in torch (tests/ddim_statement.py, tests/test_gpu_ddim_kernels.py). */
 typedef struct dv_ddim_coef {
   double sqrt_recip_alpha;   /* sqrt(1/abar_t)     acv_ddim.py:156 */
   double sqrt_recipm1_alpha; /* sqrt(1/abar_t - 1) acv_ddim.py:157 */

@@ -880,8 +880,9 @@ def _masked_metrics():
 
 
 def _ddim_step(last):
-    """The header's statement of one DDIM state update (acv_ddim.py:272-294, :318-362) in float64.  There is no test of the
-    kernel alone to copy a bar from (the loop tests compare whole trajectories), so the bars come from the number formats:
+    """The header's statement of one DDIM state update (acv_ddim.py:272-294, :318-362) in float64.  The kernel alone is held
+    branch by branch, bit for bit and to float64 ulps, by test_gpu_ddim_kernels.py against the reference's own dtypes; this
+    row is about the arena contract and keeps a float64 statement, whose bars come from the number formats:
     dq < 12 has a float32 ulp of 2^-20, the two-hot weight 2 * frac(dq) - 1 inherits at most 4 of them, and the bilinear
     /4 before it two roundings more: 1e-5 on x_start; pred_eps and x_next divide / scale that by coefficients <= 2: 2e-5.
     mask and ens are sums of a few float32 terms of size <= 1 / <= 50: 1e-6 and 1e-5."""
@@ -1447,8 +1448,8 @@ TABLE = [
     R("disparity_regression", "dv_disparity_regression_f32", _disparity_regression, "test_disparity_regression", variants="ac"),
     R("softmax_regress", "dv_softmax_regress_f32", _softmax_regress, "test_softmax_regress", variants="ac"),
     R("two_hot", "dv_encode_two_hot_f32", _two_hot, "test_encoder_golden", variants="ac"),
-    R("ddim_step", "dv_ddim_step", _ddim_step(False), "the number formats (see _ddim_step)", variants="ac"),
-    R("ddim_step_last", "dv_ddim_step", _ddim_step(True), "the number formats (see _ddim_step)", variants="ac"),
+    R("ddim_step", "dv_ddim_step", _ddim_step(False), "the number formats (see _ddim_step); test_gpu_ddim_kernels.py", variants="ac"),
+    R("ddim_step_last", "dv_ddim_step", _ddim_step(True), "the number formats (see _ddim_step); test_gpu_ddim_kernels.py", variants="ac"),
     R("masked_metrics", "dv_masked_metrics_f32", _masked_metrics, "test_metrics_golden", variants="ac", aligned=("mask",)),
     # training entries with an alignment predicate (or refusal) and no offset-view test elsewhere
     R("feature_gate_bwd_ragged", "dv_feature_gate_bwd_f32", _feature_gate_bwd((2, 16, 6, 5, 7)), "test_gate_backward",
