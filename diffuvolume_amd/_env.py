@@ -55,6 +55,12 @@ KNOBS = {
                       "batched matmuls, a softmax over a materialised [B, windows, 16, 64, 64] tensor, the 1x1x1 convolution) "
                       "instead of the fused HIP forward of csrc/window_attn.hip and the atomics-free HIP backward of "
                       "csrc/window_attn_bwd.hip (A/B runs, tests)"),
+    "DV_TRAIN_NET2D": ("torch", "train_net2d.route() on the 2-D networks of ACVNet_DDIM / PWCNet_ddim training: both feature "
+                       "CNNs, ACV's concatconv, the BatchNorm2d layers of refinenet3 and the resize of PCW's refinement feature",
+                       "hip = Conv2d + BatchNorm2d + ReLU / Mish (+ the BasicBlock's skip) on the HIP convolution routes of "
+                       "train2d and the fused kernels of csrc/bn3d_act.hip, and F.interpolate(bilinear, align_corners=True) "
+                       "on the inference kernel with the atomics-free backward of csrc/resize_bwd.hip, so that every "
+                       "gradient repeats bit for bit; torch = the nn.Module calls (MIOpen, ATen's atomic resize backward)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

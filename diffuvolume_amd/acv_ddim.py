@@ -15,7 +15,8 @@ The dead pre-DDIM aggregation pass of the reference's eval branch (acv_ddim.py:3
 its result ``pred2`` is never returned) is skipped; outputs are unchanged.
 Training (``model.train()``, the reference's :424-482 branch): ``forward`` returns
 ``[pred_attention, pred0, pred1, pred2]`` with the 3-D convolutions on the differentiable HIP route of
-``train3d.py``, the patch stencils on ``train_patch.py``, the hourglasses' window attention on ``train_attn.py`` and
+``train3d.py``, the patch stencils on ``train_patch.py``, the hourglasses' window attention on ``train_attn.py``, the
+feature CNN and ``concatconv`` on the nn.Modules or -- with ``DV_TRAIN_NET2D=hip`` -- on ``train_net2d.py``, and
 everything else on PyTorch autograd; on CPU tensors it raises.
 """
 from __future__ import annotations
@@ -36,6 +37,7 @@ from . import train_volume
 from .train_volume import build_concat_volume_train
 from .train_patch import patch_volume_train
 from .train_attn import window_attention_train
+from . import train_net2d
 from .head import DynamicHead
 from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
@@ -122,6 +124,8 @@ class FeatureExtraction(PlanCache, nn.Module):
         return nn.Sequential(*layers)
 
     def _build_plans(self, slot):
+        if slot == train_net2d.SLOT:
+            return train_net2d.build_plans(self)
         with torch.no_grad():
             first = [_plan_cb2(self.firstconv[i], ACT_RELU) for i in (0, 2, 4)]
             stacks = [[_ResBlock2dPlan(b) for b in getattr(self, n)] for n in ("layer1", "layer2", "layer3", "layer4")]
@@ -130,6 +134,14 @@ class FeatureExtraction(PlanCache, nn.Module):
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.DiffuVolumeError(f"input is on {x.device}: the feature CNN runs on the MI355X (no CPU fallback)")
+        if self.training and train_net2d.route() == "hip":
+            # training on the HIP route: convolutions on train2d's kernels, BatchNorm2d + ReLU + skip on train_norm's
+            n = train_net2d.Net2d(self)
+            x = n.stack(self.layer1, n.seq(self.firstconv, x))
+            l2 = n.stack(self.layer2, x)
+            l3 = n.stack(self.layer3, l2)
+            l4 = n.stack(self.layer4, l3)
+            return {"gwc_feature": torch.cat((l2, l3, l4), dim=1)}
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             x = self.layer1(self.firstconv(x))          # training / autograd: the plain PyTorch modules, on the GPU
             l2 = self.layer2(x)
@@ -329,6 +341,8 @@ class _HipPlanMixin(PlanCache, nn.Module):
     """The plans of the ACV wrappers (submodule.PlanCache: rebuilt when the weights change)."""
 
     def _build_plans(self, slot) -> _Plans:
+        if slot == train_net2d.SLOT:
+            return train_net2d.build_plans(self, ("concatconv.",))
         dev = self.dres0[0][0].weight.device
         if dev.type != "cuda":
             raise _lib.DiffuVolumeError("the ACVNet hot path needs the model on the MI355X (model.cuda()); no CPU fallback")
@@ -561,8 +575,12 @@ class ACVNet_DDIM(_HipPlanMixin):
         cost_attention = self.dres2_att_(cost_attention)
         att_weights = _train_pair(self.classif_att_, cost_attention)
 
-        cl = self.concatconv(fl)
-        cr = self.concatconv(fr)
+        if train_net2d.route() == "hip":
+            n2d = train_net2d.Net2d(self, ("concatconv.",))
+            cl, cr = n2d.seq(self.concatconv, fl), n2d.seq(self.concatconv, fr)
+        else:
+            cl = self.concatconv(fl)
+            cr = self.concatconv(fr)
         # :388-390 `F.softmax(att_weights, dim=2) * concat_volume`, and :451 `* noisy` below, as factors: the softmax on
         # the [B,1,D,h,w] logits, both products on the [B,D,h,w] scale of build_concat_volume_train.  (p * n) * v instead
         # of the reference's (p * v) * n: at most one rounding per element, the order of the eval path

@@ -18,7 +18,8 @@ q_sample(asd), thresholds dif<1 & unc<1, ensemble [0.9,0,0,0.1], Mish activation
 Training (``model.train()``, the reference's :643-735 branch): ``forward`` returns
 ``[pred0, combine, pred1, pred2, pred3, disp_finetune]`` with the 3-D convolutions on ``train3d.py``, the BatchNorm3d +
 Mish behind them on ``train_norm.py``, the 2-D convolutions of ``refinenet3`` on ``train2d.py`` and the rest (feature
-CNN, BatchNorm2d and its Mish, ``dispupsample`` in float64) on PyTorch autograd; on CPU tensors it raises.
+CNN, BatchNorm2d and its Mish, the resize of ``finetune_feature``; ``dispupsample`` in float64) on PyTorch autograd -- with
+``DV_TRAIN_NET2D=hip`` the feature CNN, BatchNorm2d + Mish and the resize run on ``train_net2d.py``; on CPU tensors it raises.
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, ddim, train2d, train3d
+from . import _lib, ddim, train2d, train3d, train_net2d
 from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
 from .head import DynamicHead
 from .train_tail import regress_head
@@ -57,7 +58,8 @@ def _train_seq(seq: nn.Module, x: torch.Tensor, act: str = "none", skip: Optiona
     """A Sequential of the training graph, then `+ skip` and `act` ("none" / "mish"): 3-D convolutions on `train3d`, 2-D
     ones on `train2d` (refinenet3 only).  A BatchNorm3d goes to `train_norm.bn_act` together with what follows it -- the
     Mish behind it in the walk, or the caller's skip and activation when it ends the walk (the hourglass tails) -- so that
-    DV_TRAIN_NORM=hip runs them as one kernel; everything else (BatchNorm2d, a Mish behind something else) stays PyTorch."""
+    DV_TRAIN_NORM=hip runs them as one kernel, and with DV_TRAIN_NET2D=hip a BatchNorm2d (refinenet3) goes to
+    `train_net2d.bn_act2d` the same way; everything else (a Mish behind something else) stays PyTorch."""
     mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
     i = 0
     while i < len(mods):
@@ -70,6 +72,8 @@ def _train_seq(seq: nn.Module, x: torch.Tensor, act: str = "none", skip: Optiona
             x = _train_seq(m, x, a, s)
         elif isinstance(m, nn.BatchNorm3d):
             x = bn_act(m, x, a, s)
+        elif isinstance(m, nn.BatchNorm2d) and train_net2d.route() == "hip":
+            x = train_net2d.bn_act2d(m, x, a, s)
         else:
             if isinstance(m, nn.ConvTranspose3d):
                 x = train3d.conv_transpose3d_module(m, x)
@@ -159,6 +163,9 @@ class FeatureExtraction(PlanCache, nn.Module, _Stacker):
 
     # ---- HIP plans (csrc/conv2d.hip: BN / Mish / residual fused), rebuilt when the parameters change ----
     def _build_plans(self, slot):
+        if slot == train_net2d.SLOT:
+            return train_net2d.build_plans(self)
+
         def head(seq):          # convbn + Mish + Conv2d 1x1
             return (_plan_cb2(seq[0], ACT_MISH), Conv2dPlan(seq[2].weight, None, act=ACT_NONE))
         with torch.no_grad():
@@ -173,6 +180,8 @@ class FeatureExtraction(PlanCache, nn.Module, _Stacker):
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.DiffuVolumeError(f"input is on {x.device}: the feature CNN runs on the MI355X (no CPU fallback)")
+        if self.training and train_net2d.route() == "hip":
+            return self._forward_train_hip(x)
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             return self._forward_modules(x)
         p = self.prepare(check_weights=True)
@@ -196,6 +205,25 @@ class FeatureExtraction(PlanCache, nn.Module, _Stacker):
                 out.update(concat_feature1=run(p["lastconv"], fc), finetune_feature=run(p["refine"], fc),
                            concat_feature2=run(p["concat2"], l5), concat_feature3=run(p["concat3"], l6),
                            concat_feature4=run(p["concat4"], l7))
+        return out
+
+    def _forward_train_hip(self, x):
+        """The same graph in training on the HIP route of `train_net2d` (DV_TRAIN_NET2D=hip)."""
+        n = train_net2d.Net2d(self)
+        x = n.stack(self.layer1, n.seq(self.firstconv, x))
+        l2 = n.stack(self.layer2, x)
+        l3 = n.stack(self.layer3, l2)
+        l4 = n.stack(self.layer4, l3)
+        l5 = n.stack(self.layer5, l4)
+        l6 = n.stack(self.layer7, l5)
+        l7 = n.stack(self.layer9, l6)
+        fc = torch.cat((l2, l3, l4), dim=1)
+        out = {"gw1": n.seq(self.layer11, fc), "gw2": n.seq(self.gw2, l5), "gw3": n.seq(self.gw3, l6),
+               "gw4": n.seq(self.gw4, l7)}
+        if self.concat_feature:
+            out.update(concat_feature1=n.seq(self.lastconv, fc), finetune_feature=n.seq(self.layer_refine, fc),
+                       concat_feature2=n.seq(self.concat2, l5), concat_feature3=n.seq(self.concat3, l6),
+                       concat_feature4=n.seq(self.concat4, l7))
         return out
 
     def _forward_modules(self, x):
@@ -241,7 +269,7 @@ class RefineNet(nn.Module, _Stacker):
         x = _train_seq(nn.Sequential(self.conv1, self.conv2, self.conv3, self.conv4), x)
         for blk in (self.conv5[0], self.conv6[0], self.conv7[0]):        # BasicBlock (submodule.py:192-215)
             skip = x if blk.downsample is None else _train_seq(blk.downsample, x)
-            x = _train_seq(blk.conv2, _train_seq(blk.conv1, x)) + skip
+            x = _train_seq(blk.conv2, _train_seq(blk.conv1, x), "none", skip)
         return disp + _train_seq(self.conv8, x)
 
 
@@ -840,7 +868,9 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         pred_combine = regress_head(_train_seq(self.classif4, combine), size, align_corners=True)
 
         # refinement (:711-728)
-        rl, rr = self.refine_features(fl, fr, (hh, ww))
+        # (:487-492 on the route of train_net2d: DV_TRAIN_NET2D=hip resizes on the HIP kernel with the atomics-free backward)
+        rl = train_net2d.resize_bilinear_train(fl["finetune_feature"], (hh, ww))
+        rr = train_net2d.resize_bilinear_train(fr["finetune_feature"], (hh, ww))
         # left - warp(right, pred3) and their +-24 correlation with the HIP backward (train_refine.py; DV_TRAIN_REFINE)
         diff, corr = warp_corr_train(rl, rr, pred3, 24)
         refine_in = torch.cat((diff, rl, self._dispupsample_train(pred3), pred3, corr), dim=1)

@@ -2,8 +2,9 @@
  * builders (dv_gwc_volume_f32, dv_concat_volume_f32 / dv_concat_prob_volume_f32 of diffuvolume_hip.h), the warp +
  * correlation of PWCNet_ddim's refinement input in training, forward and backward, the BatchNorm3d (batch statistics)
  * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, the backward of the
- * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32), and the backward of the hourglass's
- * bottleneck window attention (dv_window_attn3d_f32).
+ * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32), the backward of the hourglass's
+ * bottleneck window attention (dv_window_attn3d_f32), and the backward of the align_corners=True bilinear resize
+ * (dv_resize_bilinear_ac_f32).
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -187,6 +188,21 @@ size_t dv_window_attn3d_bwd_workspace_floats(int B, int C, int D, int H, int W, 
 int dv_window_attn3d_bwd_f32(const float* x, const float* qkv_w, const float* qkv_b, const float* proj_w, const float* dout,
                              float* dx, float* dqkv_w, float* dqkv_b, float* dproj_w, float* dproj_b, float* workspace,
                              int B, int C, int D, int H, int W, int heads, dv_stream_t stream);
+
+/* ---- bilinear resize with align_corners=True, backward -------------------------------------------------------------------
+ * What autograd computes for F.interpolate(x, [H, W], mode="bilinear", align_corners=True), i.e. for the forward
+ * dv_resize_bilinear_ac_f32 (diffuvolume_hip.h), which stays as it is: its exact adjoint in its own weights.
+ *   dy [BC,H,W] -> dx [BC,h,w];  sy = (h-1)/(H-1) (0 for H == 1),  fy = sy Y,  y0 = (int)fy,  y1 = y0 + [y0 < h-1],
+ *   ly = fy - y0,  hy = 1 - ly,  all in the forward's float expressions;  x likewise
+ *   dx[bc,i,j] = sum_{Y,X} dy[bc,Y,X] (hy [y0 == i] + ly [y1 == i]) (hx [x0 == j] + lx [x1 == j])
+ * A gather (ATen's backward scatters with atomics): y0 is monotone in Y, so the rows that touch source row i are one range,
+ * found by bisection on the forward's expression.  One block per plane, band of 8 source rows and tile of 64 source
+ * columns stages the dy rows it needs in LDS, sums along X (ascending), then along Y (ascending).  16-byte loads of dy when
+ * W % 4 == 0 and dy lies on a 16-byte line, element loads otherwise, with the same bits; dx needs 4-byte alignment only.
+ * Any sizes the forward takes: H == h, h == 1, downscaling, ratios that are no integers.
+ * A NULL pointer or a non-positive size: DV_ERR_NULL (without a plane there is no element either pointer could name);
+ * more than 2^31 - 1 blocks (BC ceil(h/8) ceil(w/64)): DV_ERR_SHAPE.  dx must not overlap dy. */
+int dv_resize_bilinear_ac_bwd_f32(const float* dy, float* dx, int BC, int h, int w, int H, int W, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
