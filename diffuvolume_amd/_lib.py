@@ -208,6 +208,11 @@ VOLUME_TRAIN_SIGNATURES = {
                                  held_by("test_gpu_attn_train.py::test_attn_bwd_abi_offset_views_bounds_and_refusals")),
     "dv_resize_bilinear_ac_bwd_f32": (c_int, [P, P, I, I, I, I, I, P],
                                       held_by("test_gpu_resize_bwd.py::test_resize_bwd_abi_offset_views_bounds_and_refusals")),
+    "dv_dwconv3x3_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, I, c_float, P],
+                         held_by("test_gpu_dwconv.py::test_dwconv_abi_offset_views_bounds_and_refusals")),
+    "dv_dwconv3x3_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
+    "dv_dwconv3x3_bwd_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, P],
+                             held_by("test_gpu_dwconv.py::test_dwconv_abi_offset_views_bounds_and_refusals")),
 }
 
 

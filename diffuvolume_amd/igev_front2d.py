@@ -13,6 +13,7 @@ from torch import nn
 from .igev_layers import (ACT_RELU, HIP, TORCH, TRAIN, BasicConv_IN, Conv2x_IN, ResidualBlock, _own_route,
                           _refuse_autocast, _require_cuda, _stem, _train_mode, _wants_autograd, basic_conv_in, conv2x,
                           freeze_bn, walk)
+from .mobilenetv2 import block_on_hip
 from .submodule import PlanCache
 
 
@@ -75,8 +76,9 @@ def feature_pyramid(route, m, x):
     """Feature.forward (core/extractor.py:337-361); a feature module of another class is called as is."""
     if not isinstance(m, Feature):
         return m(x)
-    # a backbone made of plain [Conv2d, BatchNorm2d, ReLU / ReLU6] stages (synth.StubMobileNetV2) is walked on the route;
-    # anything else (timm's MobileNetV2: depth-wise / squeeze-excite blocks) is the injected module's own business
+    # a backbone made of plain [Conv2d, BatchNorm2d, ReLU / ReLU6] stages (synth.StubMobileNetV2) or of the in-tree
+    # MobileNetV2 blocks (mobilenetv2.MobileNetV2Features) is walked on the route; anything else (a timm object: its own
+    # depth-wise / squeeze-excite block classes) is the injected module's own business
     stage = partial(walk, route) if m._backbone_on_hip() else (lambda mods, t: reduce(lambda v, f: f(v), mods, t))
     x2 = stage(m.block0, stage([m.conv_stem, m.bn1, m.act1], x))
     x4 = stage(m.block1, x2)
@@ -95,7 +97,8 @@ class Feature(nn.Module):
     """core/extractor.py:327-361.  The reference takes its stem and blocks from
     ``timm.create_model('mobilenetv2_100', pretrained=True, features_only=True)``; neither timm nor the weights
     exist offline, so the backbone object is injected: anything with ``conv_stem``, ``bn1``, ``act1`` and ``blocks``
-    (7 stages with 16/24/32/64/96/160/320 output channels) -- a timm MobileNetV2 or ``synth.StubMobileNetV2``."""
+    (7 stages with 16/24/32/64/96/160/320 output channels) -- ``mobilenetv2.MobileNetV2Features`` (the real backbone
+    under timm's names, on the HIP kernels), ``synth.StubMobileNetV2`` or a timm MobileNetV2 (which runs as it is)."""
 
     def __init__(self, backbone):
         super().__init__()
@@ -121,7 +124,7 @@ class Feature(nn.Module):
                 k = m.kernel_size[0]
                 return (m.groups == 1 and m.dilation == (1, 1) and m.kernel_size == (k, k) and k in (1, 3)
                         and m.padding == (k // 2, k // 2) and m.stride[0] in (1, 2) and m.stride[0] == m.stride[1])
-            return isinstance(m, (nn.BatchNorm2d, nn.ReLU, nn.ReLU6, nn.Identity))
+            return isinstance(m, (nn.BatchNorm2d, nn.ReLU, nn.ReLU6, nn.Identity)) or block_on_hip(m)
         return all(plain(m) for m in (self.conv_stem, self.bn1, self.act1, self.block0, self.block1, self.block2,
                                       self.block3, self.block4))
 

@@ -24,7 +24,8 @@ from . import _lib, train2d, train3d
 from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv2dK4S2Plan, Deconv3dPlan, _dev_f32,
                         weight_key)
 
-ACT_RELU6 = -6                # the walkers' own code: the kernels have no ReLU6, every route spells it out
+ACT_RELU6 = -6                # the walkers' own code: `dv_dwconv3x3_f32` takes it as a capped ReLU inside the launch, the
+                              # other kernels have no ReLU6 and every route spells it out
 _PLAN_CACHE = weakref.WeakKeyDictionary()
 
 
@@ -126,6 +127,56 @@ class _FewInPlan:
         return out
 
 
+def depthwise_stride(conv: nn.Module) -> int:
+    """The stride of a depthwise 3x3 convolution as MobileNetV2 builds it -- nn.Conv2d(C, C, 3, stride, 1, groups=C,
+    bias=False) with stride 1 or 2 --; anything else raises."""
+    st = conv.stride[0] if isinstance(conv, nn.Conv2d) and not isinstance(conv, nn.ConvTranspose2d) else 0
+    if (st not in (1, 2) or conv.stride != (st, st) or conv.kernel_size != (3, 3) or conv.padding != (1, 1)
+            or conv.dilation != (1, 1) or conv.groups != conv.in_channels or conv.out_channels != conv.in_channels
+            or conv.bias is not None or conv.padding_mode != "zeros"):
+        raise _lib.DiffuVolumeError(f"depthwise Conv2d on the HIP front: kernel 3, padding 1, stride 1 or 2, groups = "
+                                    f"channels, no bias, got {conv}")
+    return st
+
+
+def hip_dwconv2d(conv: nn.Conv2d, x: torch.Tensor, bn: Optional[nn.BatchNorm2d] = None, act: int = ACT_NONE) -> torch.Tensor:
+    """``act(bn(conv(x)))`` for a depthwise 3x3 nn.Conv2d (`depthwise_stride`) with eval-mode BatchNorm folded and
+    ``act`` in ACT_NONE / ACT_RELU / ACT_RELU6 applied inside the one launch of `dv_dwconv3x3_f32`."""
+    x = _dev_f32(x, "x")
+    if bn is not None and bn.training:
+        raise _lib.DiffuVolumeError("BatchNorm2d in training mode: the HIP front folds running statistics (model.eval())")
+    key = (act, weight_key([conv.weight] + (list(_bn_tuple(bn)) if bn is not None else [])))
+    hit = _PLAN_CACHE.get(conv)
+    if hit is None or hit[0] != key:
+        _PLAN_CACHE[conv] = hit = (key, _DepthwisePlan(conv.weight, bn, depthwise_stride(conv), act))
+    return hit[1](x)
+
+
+class _DepthwisePlan:
+    """A depthwise 3x3 nn.Conv2d [+ eval BatchNorm, folded in double] [+ ReLU | ReLU6] on `dv_dwconv3x3_f32`."""
+
+    def __init__(self, w, bn, stride, act):
+        if act not in (ACT_NONE, ACT_RELU, ACT_RELU6):
+            raise _lib.DiffuVolumeError(f"depthwise Conv2d on the HIP front: no activation, ReLU or ReLU6, got {act}")
+        self.c, self.stride = w.shape[0], stride
+        self.w = _dev_f32(w.detach(), "weight").reshape(self.c, 9).contiguous()
+        self.act, self.relu_max = (ACT_RELU, 6.0) if act == ACT_RELU6 else (act, 0.0)
+        self.scale = self.shift = None
+        if bn is not None:
+            sc = (bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps))
+            self.scale = sc.float().contiguous()
+            self.shift = (bn.bias.detach().double() - bn.running_mean.detach().double() * sc).float().contiguous()
+
+    def __call__(self, x):
+        b, c, h, w = x.shape
+        if c != self.c:
+            raise RuntimeError(f"expected {self.c} channels, got {c}")
+        out = torch.empty((b, c, (h - 1) // self.stride + 1, (w - 1) // self.stride + 1), dtype=torch.float32, device=x.device)
+        _lib.launch("dv_dwconv3x3_f32", x.device, x.data_ptr(), self.w.data_ptr(), _lib.ptr(self.scale), _lib.ptr(self.shift),
+                    out.data_ptr(), b, c, h, w, self.stride, self.act, self.relu_max)
+        return out
+
+
 def instance_norm_act(x: torch.Tensor, act: int = ACT_NONE, eps: float = 1e-5, inplace: bool = True) -> torch.Tensor:
     """nn.InstanceNorm2d (affine=False) + activation: `dv_instance_norm_act_f32`, one block per (b, c) plane."""
     x = _dev_f32(x, "x")
@@ -143,9 +194,13 @@ class _HipRoute:
     name = "HIP"
 
     @staticmethod
-    def conv(conv, x, bn=None, act=ACT_NONE):
-        x = hip_conv2d(conv, x, bn, ACT_RELU if act == ACT_RELU6 else act)
+    def conv(conv, x, bn=None, act=ACT_NONE, residual=None):
+        x = hip_conv2d(conv, x, bn, ACT_RELU if act == ACT_RELU6 else act, residual)
         return x.clamp_(max=6.0) if act == ACT_RELU6 else x
+
+    @staticmethod
+    def dwconv(conv, x, bn=None, act=ACT_NONE):
+        return hip_dwconv2d(conv, x, bn, act)
 
     @staticmethod
     def conv_in(conv, x, inorm, act=ACT_NONE, torch_norm=False):
@@ -165,11 +220,16 @@ class _AutogradRoute:
     runs InstanceNorm.  ``torch_norm`` (TRAIN only has the choice): PyTorch's InstanceNorm2d instead of the HIP pass --
     the spx heads of the upsampler train on it, and the two do not give the same bits."""
 
-    def __init__(self, name, raw_conv, hip_inorm):
-        self.name, self.raw_conv, self.hip_inorm = name, raw_conv, hip_inorm
+    def __init__(self, name, raw_conv, raw_dwconv, hip_inorm):
+        self.name, self.raw_conv, self.raw_dwconv, self.hip_inorm = name, raw_conv, raw_dwconv, hip_inorm
 
-    def conv(self, conv, x, bn=None, act=ACT_NONE):
+    def conv(self, conv, x, bn=None, act=ACT_NONE, residual=None):
         x = self.raw_conv(conv, x)
+        x = x if bn is None else bn(x)
+        return _TORCH_ACT[act](x if residual is None else residual + x)
+
+    def dwconv(self, conv, x, bn=None, act=ACT_NONE):
+        x = self.raw_dwconv(conv, x)
         return _TORCH_ACT[act](x if bn is None else bn(x))
 
     def conv_in(self, conv, x, inorm, act=ACT_NONE, torch_norm=False):
@@ -188,9 +248,13 @@ def _train_conv(conv, x):
     return train2d.conv_transpose2d_module(conv, x) if isinstance(conv, nn.ConvTranspose2d) else train2d.conv2d_any(conv, x)
 
 
+def _train_dwconv(conv, x):
+    return train2d.dwconv2d(x, conv.weight, depthwise_stride(conv))
+
+
 HIP = _HipRoute()
-TORCH = _AutogradRoute("torch", lambda conv, x: conv(x), hip_inorm=False)
-TRAIN = _AutogradRoute("training", _train_conv, hip_inorm=True)
+TORCH = _AutogradRoute("torch", lambda conv, x: conv(x), lambda conv, x: conv(x), hip_inorm=False)
+TRAIN = _AutogradRoute("training", _train_conv, _train_dwconv, hip_inorm=True)
 
 
 def _own_route(*xs):

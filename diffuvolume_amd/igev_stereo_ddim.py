@@ -6,8 +6,10 @@ reference's, so its checkpoints load with strict=True.  It is assembled from pie
   igev_volume    FeatureAtt, hourglass, IGEVCostVolume: gwc volume -> hourglass(8) -> initial disparity
   igev_upsample  context_upsample, IGEVUpsampler: the spx heads and the convex upsampling
   igev_loop      DynamicHead180, IGEVDiffusionLoop: the DDIM volume-filter loop around the GRU iterations
-All of it runs on HIP kernels; only the MobileNetV2 backbone is injected (``Feature(backbone)``): timm and its pretrained
-weights are the caller's.  Every name of the five modules is importable from here too."""
+All of it runs on HIP kernels.  The MobileNetV2 backbone is injected (``Feature(backbone)``):
+``mobilenetv2.MobileNetV2Features()`` is the real network under timm's parameter names and runs on the HIP kernels too
+(depthwise 3x3 on csrc/dwconv2d.hip); a timm object runs as it is, and the pretrained weights are the caller's either
+way.  Every name of the five modules is importable from here too."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -60,7 +62,8 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
                 raise _lib.DiffuVolumeError(
                     "IGEVStereo_ddim(args) builds its feature pyramid from timm.create_model('mobilenetv2_100', "
                     "pretrained=True, features_only=True) like the reference (core/extractor.py:331); timm is not "
-                    "importable here -- pass feature=Feature(backbone) (a timm model or synth.StubMobileNetV2())")
+                    "importable here -- pass feature=Feature(backbone) (mobilenetv2.MobileNetV2Features(), the same "
+                    "network under timm's parameter names, a timm model or synth.StubMobileNetV2())")
             feature = Feature(timm.create_model("mobilenetv2_100", pretrained=True, features_only=True))
         self.args = args
         self.scale = 1.0

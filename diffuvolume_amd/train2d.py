@@ -39,7 +39,11 @@ part: ``conv2d_s2`` (3x3, stride 2: forward on ``Conv2dPlan(stride=2)``, both gr
 kernels above through an exact identity), ``conv2d_k1s2`` (the 1x1 stride-2 ``downsample``), ``conv2d_fewin`` (the image
 convolutions: weight gradient on ``dv_conv2d_fewin_wgrad_f32``, no input gradient), ``instance_norm_act`` (backward on
 ``dv_instance_norm_act_bwd_f32``, both csrc/igev_front_bwd.hip) and the dispatcher ``conv2d_any``.  Plans are built per
-call: these layers run once per pair."""
+call: these layers run once per pair.
+
+The MobileNetV2 backbone of that front (``mobilenetv2.MobileNetV2Features``) adds ``dwconv2d``, the depthwise 3x3
+convolution of its blocks (csrc/dwconv2d.hip, forward and backward).  ``conv2d_any`` keeps refusing grouped
+convolutions: a depthwise layer reaches ``dwconv2d`` through the backbone's block classes only."""
 from __future__ import annotations
 
 import ctypes
@@ -671,6 +675,51 @@ def instance_norm_act(x: torch.Tensor, act: int = ACT_NONE, eps: float = 1e-5) -
         y = F.instance_norm(x, eps=eps)
         return y if act == ACT_NONE else (F.relu(y) if act == ACT_RELU else F.leaky_relu(y, 0.01))
     return InstanceNormActFn.apply(x, act, eps)
+
+
+class DepthwiseConv2dFn(torch.autograd.Function):
+    """The bare depthwise 3x3 convolution (padding 1, stride 1 / 2, no bias): forward on ``dv_dwconv3x3_f32`` without scale,
+    shift or activation, both gradients on ``dv_dwconv3x3_bwd_f32`` (csrc/dwconv2d.hip).  Only ``x`` is kept for the
+    backward (beside the weight, which is the parameter itself): the output is not."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        _lib.check_f32(x, "x")
+        _lib.check_f32(weight, "weight")
+        if x.dim() != 4 or tuple(weight.shape) != (x.shape[1], 1, 3, 3) or stride not in (1, 2):
+            raise _lib.DiffuVolumeError(f"dwconv2d: x {tuple(x.shape)}, weight {tuple(weight.shape)}, stride {stride}")
+        x, wt = x.contiguous(), weight.detach().contiguous()
+        b, c, h, w = x.shape
+        out = torch.empty((b, c, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.float32, device=x.device)
+        _lib.launch("dv_dwconv3x3_f32", x.device, x.data_ptr(), wt.data_ptr(), 0, 0, out.data_ptr(), b, c, h, w, stride,
+                    ACT_NONE, 0.0)
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        g, wt = g.contiguous(), weight.detach().contiguous()
+        b, c, h, w = x.shape
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = ws = None
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(wt)
+            ws = _lib.workspace("dv_dwconv3x3_bwd_workspace_floats", x.device, b, c, h, w, ctx.stride)
+        if dx is not None or dw is not None:
+            _lib.launch("dv_dwconv3x3_bwd_f32", x.device, x.data_ptr(), wt.data_ptr(), g.data_ptr(), _lib.ptr(dx), _lib.ptr(dw),
+                        _lib.ptr(ws), b, c, h, w, ctx.stride)
+        return dx, dw, None
+
+
+def dwconv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """F.conv2d(x, weight, None, stride, padding=1, groups=C) for a depthwise 3x3 ``weight`` [C,1,3,3] on the training
+    route."""
+    if route() == "torch":
+        _lib.check_f32(x, "x")
+        return F.conv2d(x, weight, None, stride=stride, padding=1, groups=x.shape[1])
+    return DepthwiseConv2dFn.apply(x, weight, stride)
 
 
 def conv2d_any(m: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:

@@ -3,8 +3,8 @@
  * correlation of PWCNet_ddim's refinement input in training, forward and backward, the BatchNorm3d (batch statistics)
  * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, the backward of the
  * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32), the backward of the hourglass's
- * bottleneck window attention (dv_window_attn3d_f32), and the backward of the align_corners=True bilinear resize
- * (dv_resize_bilinear_ac_f32).
+ * bottleneck window attention (dv_window_attn3d_f32), the backward of the align_corners=True bilinear resize
+ * (dv_resize_bilinear_ac_f32), and the depthwise 3x3 convolution of IGEV's MobileNetV2 backbone, forward and backward.
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -203,6 +203,47 @@ int dv_window_attn3d_bwd_f32(const float* x, const float* qkv_w, const float* qk
  * A NULL pointer or a non-positive size: DV_ERR_NULL (without a plane there is no element either pointer could name);
  * more than 2^31 - 1 blocks (BC ceil(h/8) ceil(w/64)): DV_ERR_SHAPE.  dx must not overlap dy. */
 int dv_resize_bilinear_ac_bwd_f32(const float* dy, float* dx, int BC, int h, int w, int H, int W, dv_stream_t stream);
+
+/* ---- depthwise 3x3 convolution of MobileNetV2's blocks, forward and backward ----------------------------------------------
+ * nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) as timm's mobilenetv2_100 (the backbone of KITTI15/core/extractor.py:
+ * 327-361) uses it in its DepthwiseSeparableConv and InvertedResidual blocks, with the eval BatchNorm behind it folded into
+ * scale / shift and its ReLU6 applied inside the launch:
+ *   x [B,C,H,W], w [C,9] (tap = ky*3 + kx), scale, shift [C] -> out [B,C,Ho,Wo],  Ho = (H-1)/stride + 1,  Wo = (W-1)/stride + 1
+ *   conv[b,c,oy,ox] = sum_{ky,kx} w[c,ky,kx] x[b,c, oy stride + ky - 1, ox stride + kx - 1]     (0 outside the image)
+ *   out = act(conv * scale[c] + shift[c])
+ * stride: 1 or 2 (anything else DV_ERR_UNSUPPORTED).  scale and shift: both or neither (one of them NULL: DV_ERR_NULL); NULL
+ * is the identity and skips the multiply-add.  act: DV_ACT_NONE or DV_ACT_RELU; relu_max > 0 caps a ReLU from above
+ * (min(max(v, 0), relu_max): 6 for ReLU6), 0 leaves it open.  Any other act, a negative or NaN relu_max, or a relu_max
+ * without DV_ACT_RELU: DV_ERR_UNSUPPORTED.
+ *
+ * One wave works on one tile of one (b,c) plane: a lane owns four consecutive output columns and walks a band of output
+ * rows, reading each input row once (one 16-byte quad, two at stride 2; the halo columns come from the neighbouring lanes)
+ * and keeping the three rows an output needs in registers.  The tiles depend on H and W only and are handed to a capped
+ * grid by a grid-stride loop; the nine taps are summed in the order ky, kx by one fmaf each.  So the same call gives the
+ * same bits on every launch and an item of a batch has the bits of the item run alone.  16-byte loads when W % 4 == 0 and
+ * x lies on a 16-byte line, 16-byte stores when Wo % 4 == 0 and out does, element accesses otherwise: the same arithmetic,
+ * the same bits.
+ *
+ * Backward of the bare convolution (BatchNorm and the activation are autograd nodes of their own in training):
+ *   dy [B,C,Ho,Wo] -> dx [B,C,H,W], dw [C,9]
+ *   dx[b,c,iy,ix] = sum over the taps (ky,kx) with (iy + 1 - ky) and (ix + 1 - kx) multiples of stride and the quotients
+ *                   (oy, ox) inside dy, of w[c,ky,kx] dy[b,c,oy,ox]: a gather, every element written once.  At stride 2
+ *                   the parity of iy and ix picks 1, 2, 2 or 4 taps.
+ *   dw[c,ky,kx]   = sum_{b,oy,ox} dy[b,c,oy,ox] x[b,c, oy stride + ky - 1, ox stride + kx - 1]: one partial of nine floats
+ *                   per wave tile in `workspace`, then one wave per channel adds the channel's partials in a fixed order in
+ *                   double.  No atomics.
+ * dx or dw may be NULL (not wanted; that launch is skipped and the other has the same bits); both NULL: DV_ERR_NULL.
+ * x is read only for dw and w only for dx; each is required (DV_ERR_NULL) with that output and may be NULL without it.
+ * `workspace` (dv_dwconv3x3_bwd_workspace_floats = 9 B C tiles-per-plane floats; 0 for a non-positive size or another
+ * stride) is required (DV_ERR_NULL) when dw is wanted.  dx must not overlap dy.  Gradients repeat bit for bit, and dx of
+ * a batch has the bits of its items run one by one.
+ * All three: a NULL tensor DV_ERR_NULL, a non-positive size or more than 0x7fff0000 tiles DV_ERR_SHAPE, before anything
+ * touches the device. */
+int dv_dwconv3x3_f32(const float* x, const float* w, const float* scale, const float* shift, float* out, int B, int C,
+                     int H, int W, int stride, int act, float relu_max, dv_stream_t stream);
+size_t dv_dwconv3x3_bwd_workspace_floats(int B, int C, int H, int W, int stride);
+int dv_dwconv3x3_bwd_f32(const float* x, const float* w, const float* dy, float* dx, float* dw, float* workspace, int B,
+                         int C, int H, int W, int stride, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
