@@ -10,8 +10,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int KSTEPS_MAX = 64;     // A fragments kept in registers: C <= 256
 
 // KS = MFMA k-steps (4 channels each), rounded up to the instantiation; channels past C contribute zeros

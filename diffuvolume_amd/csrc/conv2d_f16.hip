@@ -27,7 +27,6 @@
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 4, TW = 64, MT = TW / 16, KC = 32, CS = 48;
 

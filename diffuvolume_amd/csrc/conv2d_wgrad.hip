@@ -18,18 +18,13 @@
 // LDS bank map (ds_read_b32: bank = dword % 32, conflicts inside a 32-lane half): lane l reads channel l & 15 at output
 // position l >> 4 (two positions per half); per-channel strides are 2 mod 32 and the two positions are adjacent dwords
 // (the tap offset kx*d is the same for every lane): conflict-free for every dilation.
-#include "dv_common.h"
+#include "wgrad_splitk.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WG_CO = 32, WG_CI = 32, WG_THREADS = 256;
 constexpr int WG_TARGET_BLOCKS = 512;                    // two blocks per CU on 256 CUs
-constexpr long long WG_MAX_WS_FLOATS = 12ll << 20;       // workspace bound: 48 MB
 constexpr int WG_MAX_DILATION = 16;
-
-constexpr int pad_2mod32(int n) { return n + (((2 - n % 32) % 32) + 32) % 32; }
 
 // KS: kernel size; TY x TX: output brick; DMAX: largest dilation the x bands have room for
 template <int KS_, int TY_, int TX_, int DMAX_>
@@ -38,8 +33,8 @@ struct WgGeo {
   static constexpr int KT = KS * KS;
   static constexpr int P = TY * TX;
   static constexpr int ROW = TX + (KS - 1) * DMAX;        // floats per staged band row
-  static constexpr int XS = pad_2mod32(KS * TY * ROW);    // per-channel stride of the x bands
-  static constexpr int GS = pad_2mod32(P);                // per-channel stride of the g tile
+  static constexpr int XS = dv_pad_2mod32(KS * TY * ROW);    // per-channel stride of the x bands
+  static constexpr int GS = dv_pad_2mod32(P);                // per-channel stride of the g tile
   static_assert(TX % 4 == 0, "an MFMA step takes 4 positions along W");
   static_assert((WG_CI * XS + WG_CO * GS) * 4 <= 80 * 1024, "two blocks per CU");
 };
@@ -76,16 +71,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void conv2d_wgrad_kernel(WgArgs a) {
 #pragma unroll
   for (int t = 0; t < G::KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const size_t plane = (size_t)a.H * a.W;
   const float* xrd = xs + (cih * 16 + li) * G::XS;
   const float* grd = gs + (coh * 16 + li) * G::GS;
 
   for (long long br = b0; br < b1; ++br) {
-    long long r = br;
-    const int bx = (int)(r % a.nbx); r /= a.nbx;
-    const int by = (int)(r % a.nby); r /= a.nby;
-    const int b = (int)r;
+    int b, by, bx;
+    dv_brick_decode2(br, a.nby, a.nbx, b, by, bx);
     const int oy0 = by * G::TY, ox0 = bx * G::TX;
 
     __syncthreads();                                      // the previous brick's reads are done
@@ -129,18 +123,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void conv2d_wgrad_kernel(WgArgs a) {
     }
   }
 
-  // D layout: col = lane & 15 (ci), row = 4 * (lane >> 4) + r (co)
-  const int ci = ci0 + cih * 16 + li;
-  if (ci >= a.Cin) return;
-  float* out = a.ws + (size_t)split * a.Cout * a.Cin * G::KT;
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int co = co0 + coh * 16 + 4 * lk + rr;
-    if (co >= a.Cout) continue;
-    float* o = out + ((size_t)co * a.Cin + ci) * G::KT;
-#pragma unroll
-    for (int t = 0; t < G::KT; ++t) o[t] = acc[t][rr];
-  }
+  dv_wgrad_store_tile<G::KT>(a.ws, split, acc, co0 + coh * 16, ci0 + cih * 16, a.Cout, a.Cin, li, lk);
 }
 
 struct WgPlan {
@@ -156,13 +139,7 @@ WgPlan plan_of(int B, int Cin, int H, int W, int Cout) {
   p.nbricks = (long long)B * p.nby * p.nbx;
   // split K so that the grid fills the device twice over, within the workspace bound
   const long long mn = (long long)((Cout + WG_CO - 1) / WG_CO) * ((Cin + WG_CI - 1) / WG_CI);
-  long long s = (WG_TARGET_BLOCKS + mn - 1) / mn;
-  const long long per_split = (long long)Cout * Cin * G::KT;
-  const long long cap = WG_MAX_WS_FLOATS / per_split;
-  if (s > cap) s = cap;
-  if (s > p.nbricks) s = p.nbricks;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  p.splits = dv_wgrad_splits((WG_TARGET_BLOCKS + mn - 1) / mn, (long long)Cout * Cin * G::KT, p.nbricks, 1, false);
   return p;
 }
 
@@ -184,10 +161,7 @@ int launch_wgrad(const float* x, const float* g, float* dw, float* ws, int B, in
   a.nby = p.nby; a.nbx = p.nbx; a.nbricks = p.nbricks; a.splits = p.splits;
   dim3 grid((unsigned)((Cout + WG_CO - 1) / WG_CO), (unsigned)((Cin + WG_CI - 1) / WG_CI), (unsigned)p.splits);
   hipLaunchKernelGGL(conv2d_wgrad_kernel<G>, grid, dim3(WG_THREADS), 0, s, a);
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum(ws, dw, (long long)Cout * Cin * G::KT, p.splits, s);
-  return dv_launch_status();
+  return dv_splitk_finish(ws, dw, (long long)Cout * Cin * G::KT, p.splits, s, false);
 }
 
 }  // namespace

@@ -39,15 +39,13 @@
 // is no multiple of the brick meets a 0 of g: 0 * Inf = NaN in dW where the exact sum has no such product, as in
 // csrc/conv2d_wgrad_cat.hip.  It stays in the rows of dW that belong to that input channel; an Inf of g stays in the rows
 // of its output channel.
-//
-// Also here: the ConvGRU gate arithmetic of the training forward with the fp16 rounding points of conv2d_f16.hip's
-// epilogues (dv_gru_reset_mul_f16, dv_gru_blend_f16).
-#include "dv_common.h"
+// (The ConvGRU gate arithmetic of this route, with the fp16 rounding points of conv2d_f16.hip's epilogues, is in
+// csrc/gru_gates.hip.)
+#include "wgrad_splitk.h"
 
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HW_CO = 64, HW_CI = 64, HW_THREADS = 256;
@@ -55,8 +53,6 @@ constexpr int HW_TY = 4, HW_TX = 32;                     // output brick: TY MFM
 constexpr int HW_RS = 40;                                // halves per staged x row: [.. 7 = left halo | 8..39 | 40 = right halo]
 constexpr int HW_X0 = 8;                                 // half of interior column 0 in its row
 constexpr int HW_TARGET_BLOCKS = 256;                    // one block per CU on 256 CUs, one round
-constexpr long long HW_MAX_WS_FLOATS = 12ll << 20;       // workspace bound: 48 MB
-constexpr int HW_MAX_INPUTS = 4;
 
 template <int KS_>
 struct HwGeo {
@@ -78,26 +74,6 @@ struct HwGeo {
   static_assert((HW_CI * XS + 8 + HW_CO * GS) * 2 <= 64 * 1024, "static LDS");
 };
 
-struct HwArgs {
-  const float* src[HW_MAX_INPUTS];   // [B, c_i, H, W]
-  int coff[HW_MAX_INPUTS + 1];       // first channel of source i in the concatenation; coff[n..4] = Cin
-  const float* g;                    // [B, Cout, H, W]
-  float* ws;                         // [splits, Cout, Cin, KT]
-  int B, Cin, H, W, Cout;
-  int nby, nbx, splits;
-  long long nbricks;
-};
-
-// plane of channel ci (< Cin) of the concatenation, batch item b
-__device__ __forceinline__ const float* hw_plane(const HwArgs& a, int ci, int b, size_t plane) {
-  const float* p = a.src[0];
-  int lo = 0, hi = a.coff[1];
-  if (ci >= a.coff[1]) { p = a.src[1]; lo = a.coff[1]; hi = a.coff[2]; }
-  if (ci >= a.coff[2]) { p = a.src[2]; lo = a.coff[2]; hi = a.coff[3]; }
-  if (ci >= a.coff[3]) { p = a.src[3]; lo = a.coff[3]; hi = a.coff[4]; }
-  return p + ((size_t)b * (hi - lo) + (ci - lo)) * plane;
-}
-
 template <class G>
 struct HwRegs {
   float x[G::NX];
@@ -110,11 +86,9 @@ struct HwRegs {
 // half-waves of a wave hold rows 2 w and 2 w + 1: the same channel for every pass (HR and TY are even), so the plane's
 // base is a scalar; the (channel, row) pattern repeats every PER passes, PER offsets per thread serve all of them.
 template <class G>
-__device__ __forceinline__ void hw_load(const HwArgs& a, long long br, int co0, int ci0, int tid, HwRegs<G>& r) {
-  long long q = br;
-  const int bx = (int)(q % a.nbx); q /= a.nbx;
-  const int by = (int)(q % a.nby); q /= a.nby;
-  const int b = (int)q;
+__device__ __forceinline__ void hw_load(const DvCatArgs& a, long long br, int co0, int ci0, int tid, HwRegs<G>& r) {
+  int b, by, bx;
+  dv_brick_decode2(br, a.nby, a.nbx, b, by, bx);
   const int oy0 = by * HW_TY, ox0 = bx * HW_TX;
   const size_t plane = (size_t)a.H * a.W;
   const int col = tid & 31, rw = tid >> 5;
@@ -129,7 +103,7 @@ __device__ __forceinline__ void hw_load(const HwArgs& a, long long br, int co0, 
     for (int m = 0; m < G::NX / G::PER; ++m) {
       const int ci = ci0 + c + m * G::CPP;
       float v = 0.f;
-      if (in && ci < a.Cin) v = hw_plane(a, ci, b, plane)[off];
+      if (in && ci < a.Cin) v = dv_cat_plane(a, ci, b, plane)[off];
       r.x[m * G::PER + t] = v;
     }
   }
@@ -140,7 +114,7 @@ __device__ __forceinline__ void hw_load(const HwArgs& a, long long br, int co0, 
       const int iy = oy0 + hr - G::HALO, ci = ci0 + c, hx = (i & 1) ? ox0 + HW_TX : ox0 - 1;
       float v = 0.f;
       if (iy >= 0 && iy < a.H && hx >= 0 && hx < a.W && ci < a.Cin)
-        v = hw_plane(a, ci, b, plane)[(unsigned)(iy * a.W + hx)];
+        v = dv_cat_plane(a, ci, b, plane)[(unsigned)(iy * a.W + hx)];
       r.e[j] = v;
     }
   }
@@ -203,7 +177,7 @@ __device__ __forceinline__ void hw_store(_Float16* xs, _Float16* gs, int tid, co
 __device__ __forceinline__ unsigned hw_align(unsigned lo, unsigned hi) { return (lo >> 16) | (hi << 16); }
 
 template <class G>
-__global__ __launch_bounds__(HW_THREADS, 1) void conv2d_wgrad_cat_f16_kernel(HwArgs a) {
+__global__ __launch_bounds__(HW_THREADS, 1) void conv2d_wgrad_cat_f16_kernel(DvCatArgs a) {
   __shared__ __attribute__((aligned(16))) _Float16 xs[HW_CI * G::XS + 8];
   __shared__ __attribute__((aligned(16))) _Float16 gs[HW_CO * G::GS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -217,7 +191,8 @@ __global__ __launch_bounds__(HW_THREADS, 1) void conv2d_wgrad_cat_f16_kernel(HwA
 #pragma unroll
     for (int t = 0; t < G::KT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const _Float16* xrd = xs + (ciw * 32 + li) * G::XS + 8 * lk;
   const _Float16* grd = gs + (cow * 32 + li) * G::GS + 8 * lk;
 
@@ -263,21 +238,10 @@ __global__ __launch_bounds__(HW_THREADS, 1) void conv2d_wgrad_cat_f16_kernel(HwA
     }
   }
 
-  // D layout: col = lane & 15 (ci), row = 4 * (lane >> 4) + r (co)
-  float* out = a.ws + (size_t)split * a.Cout * a.Cin * G::KT;
 #pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int ci = ci0 + ciw * 32 + (m & 1) * 16 + li;
-    if (ci >= a.Cin) continue;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int co = co0 + cow * 32 + (m >> 1) * 16 + 4 * lk + rr;
-      if (co >= a.Cout) continue;
-      float* o = out + ((size_t)co * a.Cin + ci) * G::KT;
-#pragma unroll
-      for (int t = 0; t < G::KT; ++t) o[t] = acc[m][t][rr];
-    }
-  }
+  for (int m = 0; m < 4; ++m)
+    dv_wgrad_store_tile<G::KT>(a.ws, split, acc[m], co0 + cow * 32 + (m >> 1) * 16, ci0 + ciw * 32 + (m & 1) * 16, a.Cout,
+                               a.Cin, li, lk);
 }
 
 struct HwPlan {
@@ -293,88 +257,28 @@ HwPlan hw_plan(int B, int Cin, int H, int W, int Cout, int k) {
   // split K so that the grid fills the device once (a block has a CU to itself), within the workspace bound, at least
   // two bricks per split
   const long long mn = (long long)((Cout + HW_CO - 1) / HW_CO) * ((Cin + HW_CI - 1) / HW_CI);
-  long long s = HW_TARGET_BLOCKS / mn;
-  const long long cap = HW_MAX_WS_FLOATS / ((long long)Cout * Cin * k * k);
-  if (s > cap) s = cap;
-  if (s > p.nbricks / 2) s = p.nbricks / 2;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  p.splits = dv_wgrad_splits(HW_TARGET_BLOCKS / mn, (long long)Cout * Cin * k * k, p.nbricks, 2, false);
   return p;
-}
-
-// sum of the channel counts, or 0 when the description of the sources is unusable
-long long hw_cin(const int* channels, int n_inputs) {
-  if (channels == nullptr || n_inputs < 1 || n_inputs > HW_MAX_INPUTS) return 0;
-  long long c = 0;
-  for (int i = 0; i < n_inputs; ++i) {
-    if (channels[i] <= 0) return 0;
-    c += channels[i];
-  }
-  return c > 0x3fffffff ? 0 : c;
 }
 
 bool hw_valid(long long cin, int B, int H, int W, int Cout, int k) {
   return (k == 1 || k == 3) && cin > 0 && B > 0 && H > 0 && W > 0 && Cout > 0 && (long long)H * W < (1ll << 30) &&
-         (long long)Cout * cin * k * k <= HW_MAX_WS_FLOATS && (Cout + HW_CO - 1) / HW_CO <= 65535 &&
+         (long long)Cout * cin * k * k <= DV_WGRAD_MAX_WS_FLOATS && (Cout + HW_CO - 1) / HW_CO <= 65535 &&
          (cin + HW_CI - 1) / HW_CI <= 65535;
 }
 
 template <class G>
-int hw_launch(const HwArgs& a, float* dw, hipStream_t s) {
+int hw_launch(const DvCatArgs& a, float* dw, hipStream_t s) {
   dim3 grid((unsigned)((a.Cout + HW_CO - 1) / HW_CO), (unsigned)((a.Cin + HW_CI - 1) / HW_CI), (unsigned)a.splits);
   hipLaunchKernelGGL(conv2d_wgrad_cat_f16_kernel<G>, grid, dim3(HW_THREADS), 0, s, a);
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum(a.ws, dw, (long long)a.Cout * a.Cin * G::KT, a.splits, s);
-  return dv_launch_status();
-}
-
-// ---- ConvGRU gate arithmetic of the training forward under fp16 autocast (update.py:36-39) --------------------------
-// The epilogue chain of conv2d_f16.hip, operation for operation: every elementwise RESULT is rounded to fp16, the
-// operands are taken as they are (fp16-exact on the route; on any other float32 input the kernels still give the bits of
-// the eval forward's epilogues under fp16 autocast, which do not round them either).
-__device__ __forceinline__ float hr16(float v) { return (float)(_Float16)v; }
-__device__ __forceinline__ float gru_mul16(float r, float h) { return hr16(r * h); }
-__device__ __forceinline__ float gru_blend16(float z, float q, float h) {
-  return hr16(hr16(hr16(1.0f - z) * h) + hr16(z * q));
-}
-
-template <int V>
-__global__ __launch_bounds__(256) void gru_mul_f16_kernel(const float* __restrict__ r, const float* __restrict__ h,
-                                                          float* __restrict__ rh, size_t n) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nv = V == 4 ? n / 4 : 0;
-  for (size_t i = i0; i < nv; i += stride) {
-    const float4 a = ((const float4*)r)[i], b = ((const float4*)h)[i];
-    ((float4*)rh)[i] = make_float4(gru_mul16(a.x, b.x), gru_mul16(a.y, b.y), gru_mul16(a.z, b.z), gru_mul16(a.w, b.w));
-  }
-  for (size_t i = nv * 4 + i0; i < n; i += stride) rh[i] = gru_mul16(r[i], h[i]);
-}
-
-template <int V>
-__global__ __launch_bounds__(256) void gru_blend_f16_kernel(const float* __restrict__ z, const float* __restrict__ q,
-                                                            const float* __restrict__ h, float* __restrict__ out,
-                                                            size_t n) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nv = V == 4 ? n / 4 : 0;
-  for (size_t i = i0; i < nv; i += stride) {
-    const float4 a = ((const float4*)z)[i], b = ((const float4*)q)[i], c = ((const float4*)h)[i];
-    ((float4*)out)[i] = make_float4(gru_blend16(a.x, b.x, c.x), gru_blend16(a.y, b.y, c.y), gru_blend16(a.z, b.z, c.z),
-                                    gru_blend16(a.w, b.w, c.w));
-  }
-  for (size_t i = nv * 4 + i0; i < n; i += stride) out[i] = gru_blend16(z[i], q[i], h[i]);
-}
-
-unsigned gru16_grid(size_t n) {
-  const size_t nb = (n / 4 + 255) / 256 + 1;
-  return (unsigned)(nb < 4096 ? nb : 4096);
+  return dv_splitk_finish(a.ws, dw, (long long)a.Cout * a.Cin * G::KT, a.splits, s, false);
 }
 
 }  // namespace
 
 extern "C" size_t dv_conv2d_wgrad_cat_f16_workspace_floats(const int* channels, int n_inputs, int B, int H, int W,
                                                            int Cout, int k) {
-  const long long cin = hw_cin(channels, n_inputs);
+  const long long cin = dv_cat_cin(channels, n_inputs);
   if (!hw_valid(cin, B, H, W, Cout, k)) return 0;
   const HwPlan p = hw_plan(B, (int)cin, H, W, Cout, k);
   return (size_t)p.splits * Cout * cin * k * k;
@@ -389,50 +293,16 @@ extern "C" int dv_conv2d_wgrad_cat_f16(const float* const* inputs, const int* ch
   DV_REQUIRE_PTR(g);
   DV_REQUIRE_PTR(dw);
   DV_REQUIRE_PTR(workspace);
-  DV_REQUIRE(n_inputs >= 1 && n_inputs <= HW_MAX_INPUTS, DV_ERR_SHAPE);
-  const long long cin = hw_cin(channels, n_inputs);
+  DV_REQUIRE(n_inputs >= 1 && n_inputs <= DV_CAT_MAX_INPUTS, DV_ERR_SHAPE);
+  const long long cin = dv_cat_cin(channels, n_inputs);
   DV_REQUIRE(hw_valid(cin, B, H, W, Cout, k), DV_ERR_SHAPE);
   for (int i = 0; i < n_inputs; ++i) DV_REQUIRE_PTR(inputs[i]);
   const HwPlan p = hw_plan(B, (int)cin, H, W, Cout, k);
-  HwArgs a;
-  int off = 0;
-  for (int i = 0; i < HW_MAX_INPUTS; ++i) {
-    a.src[i] = inputs[i < n_inputs ? i : 0];
-    a.coff[i] = i < n_inputs ? off : (int)cin;
-    if (i < n_inputs) off += channels[i];
-  }
-  a.coff[HW_MAX_INPUTS] = (int)cin;
+  DvCatArgs a;
+  dv_cat_fill(a, inputs, channels, n_inputs, (int)cin);
   a.g = g; a.ws = workspace;
-  a.B = B; a.Cin = (int)cin; a.H = H; a.W = W; a.Cout = Cout;
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout;
   a.nby = p.nby; a.nbx = p.nbx; a.splits = p.splits; a.nbricks = p.nbricks;
   hipStream_t s = (hipStream_t)stream;
   return k == 1 ? hw_launch<HwGeo<1>>(a, dw, s) : hw_launch<HwGeo<3>>(a, dw, s);
-}
-
-extern "C" int dv_gru_reset_mul_f16(const float* r, const float* h, float* rh, size_t n, dv_stream_t stream) {
-  DV_REQUIRE_PTR(r);
-  DV_REQUIRE_PTR(h);
-  DV_REQUIRE_PTR(rh);
-  DV_REQUIRE(n > 0, DV_ERR_SHAPE);
-  hipStream_t s = (hipStream_t)stream;
-  if (dv_aligned16(r) && dv_aligned16(h) && dv_aligned16(rh))
-    hipLaunchKernelGGL(gru_mul_f16_kernel<4>, dim3(gru16_grid(n)), dim3(256), 0, s, r, h, rh, n);
-  else
-    hipLaunchKernelGGL(gru_mul_f16_kernel<1>, dim3(gru16_grid(n)), dim3(256), 0, s, r, h, rh, n);
-  return dv_launch_status();
-}
-
-extern "C" int dv_gru_blend_f16(const float* z, const float* q, const float* h, float* out, size_t n,
-                                dv_stream_t stream) {
-  DV_REQUIRE_PTR(z);
-  DV_REQUIRE_PTR(q);
-  DV_REQUIRE_PTR(h);
-  DV_REQUIRE_PTR(out);
-  DV_REQUIRE(n > 0, DV_ERR_SHAPE);
-  hipStream_t s = (hipStream_t)stream;
-  if (dv_aligned16(z) && dv_aligned16(q) && dv_aligned16(h) && dv_aligned16(out))
-    hipLaunchKernelGGL(gru_blend_f16_kernel<4>, dim3(gru16_grid(n)), dim3(256), 0, s, z, q, h, out, n);
-  else
-    hipLaunchKernelGGL(gru_blend_f16_kernel<1>, dim3(gru16_grid(n)), dim3(256), 0, s, z, q, h, out, n);
-  return dv_launch_status();
 }

@@ -16,7 +16,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // (the timing-only ablation switches of round 5 -- no raw loads / LDS commits / weight DMA / barrier / input transform /

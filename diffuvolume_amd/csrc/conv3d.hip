@@ -31,8 +31,6 @@ std::atomic<int> g_s2_tile_pin{0};
 std::atomic<long long> g_c1z_min_tiles{64};
 std::atomic<int> g_c1z_pin_zs{0};
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int round_mod(int v, int mod, int rem) {  // smallest v' >= v with v' % mod == rem
   int r = v % mod;
   return r <= rem ? v + (rem - r) : v + (mod - r) + rem;

@@ -21,7 +21,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 constexpr int TD = 2, TH = 4, MTX = 3, NT = 2, KC = 8;

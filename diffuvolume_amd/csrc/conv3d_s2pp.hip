@@ -45,7 +45,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // (the timing-only ablation switches this kernel was developed with -- no B loads, no brick copies, no patch reads, no step

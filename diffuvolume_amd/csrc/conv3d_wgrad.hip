@@ -15,17 +15,12 @@
 // position k = l >> 4 (two positions per half), so per-channel strides are 2 mod 32 and the two positions are adjacent
 // dwords: conflict-free.  For stride 2 the x rows are stored phase-split (even columns, then odd columns), so the
 // positions 2o + tx of one MFMA step are adjacent there too.
-#include "dv_common.h"
+#include "wgrad_splitk.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WG_CO = 32, WG_CI = 32, WG_THREADS = 256;
 constexpr int WG_TARGET_BLOCKS = 512;                    // two blocks per CU on 256 CUs
-constexpr long long WG_MAX_WS_FLOATS = 12ll << 20;       // workspace bound: 48 MB
-
-constexpr int pad_2mod32(int n) { return n + (((2 - n % 32) % 32) + 32) % 32; }
 
 template <int KS_, int S_, int TZ_, int TY_, int TX_>
 struct WgGeo {
@@ -35,8 +30,8 @@ struct WgGeo {
   static constexpr int EZ = S * (TZ - 1) + KS, EY = S * (TY - 1) + KS, EX = S * (TX - 1) + KS;
   static constexpr int EXH = (EX + S - 1) / S;           // columns per phase
   static constexpr int ROW = S * EXH;                    // floats per staged (z, y) row
-  static constexpr int XS = pad_2mod32(EZ * EY * ROW);   // per-channel stride of the x tile
-  static constexpr int GS = pad_2mod32(P);               // per-channel stride of the g tile
+  static constexpr int XS = dv_pad_2mod32(EZ * EY * ROW);   // per-channel stride of the x tile
+  static constexpr int GS = dv_pad_2mod32(P);               // per-channel stride of the g tile
   static_assert(TX % 4 == 0, "an MFMA step takes 4 positions along W");
   static_assert((WG_CI * XS + WG_CO * GS) * 4 <= 80 * 1024, "two blocks per CU");
 };
@@ -72,17 +67,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void conv3d_wgrad_kernel(WgArgs a) {
 #pragma unroll
   for (int t = 0; t < G::KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const size_t xplane = (size_t)a.D * a.H * a.W, gplane = (size_t)a.Do * a.Ho * a.Wo;
   const float* xrd = xs + (cih * 16 + li) * G::XS;
   const float* grd = gs + (coh * 16 + li) * G::GS;
 
   for (long long br = b0; br < b1; ++br) {
-    long long r = br;
-    const int bx = (int)(r % a.nbx); r /= a.nbx;
-    const int by = (int)(r % a.nby); r /= a.nby;
-    const int bz = (int)(r % a.nbz); r /= a.nbz;
-    const int b = (int)r;
+    int b, bz, by, bx;
+    dv_brick_decode3(br, a.nbz, a.nby, a.nbx, b, bz, by, bx);
     const int oz0 = bz * G::TZ, oy0 = by * G::TY, ox0 = bx * G::TX;
     const int iz0 = oz0 * G::S - PAD, iy0 = oy0 * G::S - PAD, ix0 = ox0 * G::S - PAD;
 
@@ -137,18 +130,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void conv3d_wgrad_kernel(WgArgs a) {
     }
   }
 
-  // D layout: col = lane & 15 (ci), row = 4 * (lane >> 4) + r (co)
-  const int ci = ci0 + cih * 16 + li;
-  if (ci >= a.Cin) return;
-  float* out = a.ws + (size_t)split * a.Cout * a.Cin * G::KT;
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int co = co0 + coh * 16 + 4 * lk + rr;
-    if (co >= a.Cout) continue;
-    float* o = out + ((size_t)co * a.Cin + ci) * G::KT;
-#pragma unroll
-    for (int t = 0; t < G::KT; ++t) o[t] = acc[t][rr];
-  }
+  dv_wgrad_store_tile<G::KT>(a.ws, split, acc, co0 + coh * 16, ci0 + cih * 16, a.Cout, a.Cin, li, lk);
 }
 
 struct WgPlan {
@@ -169,13 +151,7 @@ WgPlan plan_of(int B, int Cin, int D, int H, int W, int Cout) {
   p.nbricks = (long long)B * p.nbz * p.nby * p.nbx;
   // split K so that the grid fills the device twice over, within the workspace bound
   const long long mn = (long long)((Cout + WG_CO - 1) / WG_CO) * ((Cin + WG_CI - 1) / WG_CI);
-  long long s = (WG_TARGET_BLOCKS + mn - 1) / mn;
-  const long long per_split = (long long)Cout * Cin * G::KT;
-  const long long cap = WG_MAX_WS_FLOATS / per_split;
-  if (s > cap) s = cap;
-  if (s > p.nbricks) s = p.nbricks;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  p.splits = dv_wgrad_splits((WG_TARGET_BLOCKS + mn - 1) / mn, (long long)Cout * Cin * G::KT, p.nbricks, 1, false);
   return p;
 }
 
@@ -193,10 +169,7 @@ int launch_wgrad(const float* x, const float* g, float* dw, float* ws, int B, in
   a.nbz = p.nbz; a.nby = p.nby; a.nbx = p.nbx; a.nbricks = p.nbricks; a.splits = p.splits;
   dim3 grid((unsigned)((Cout + WG_CO - 1) / WG_CO), (unsigned)((Cin + WG_CI - 1) / WG_CI), (unsigned)p.splits);
   hipLaunchKernelGGL(conv3d_wgrad_kernel<G>, grid, dim3(WG_THREADS), 0, s, a);
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum(ws, dw, (long long)Cout * Cin * G::KT, p.splits, s);
-  return dv_launch_status();
+  return dv_splitk_finish(ws, dw, (long long)Cout * Cin * G::KT, p.splits, s, false);
 }
 
 }  // namespace

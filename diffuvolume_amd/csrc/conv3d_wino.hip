@@ -22,7 +22,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int round_up_mod64_32(int v) {   // smallest v' >= v with v' % 64 == 32

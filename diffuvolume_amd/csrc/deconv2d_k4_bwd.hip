@@ -26,11 +26,9 @@
 // l >> 4, channel stride 2 mod 32: conflict-free.
 // Registers (hipcc -O3 -fno-slp-vectorize, gfx950): <NT 2, 4 waves> (32 -> 32) 84 VGPR, 14.8 KB LDS; <NT 4, 3 waves>
 // (64 -> 9) 149 VGPR, 21.7 KB LDS; no instantiation spills (<4, 1> takes all 256).
-#include "dv_common.h"
+#include "wgrad_splitk.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int D2_TY = 4, D2_TX = 16, D2_P = D2_TY * D2_TX;       // brick of input pixels
 constexpr int D2_EY = 2 * D2_TY + 2, D2_EX = 2 * D2_TX + 2;      // g rows 2*oy0-1 .. 2*oy0+2*TY, columns alike
@@ -39,7 +37,6 @@ constexpr int D2_HS = D2_EY * D2_ROW;                            // per-channel 
 constexpr int D2_XS = D2_P + 2;                                  // per-channel stride of the x tile
 constexpr int D2_MAX_CO = 4, D2_MAX_NT = 4;
 constexpr int D2_TARGET_BLOCKS = 1024;                           // four blocks per CU on 256 CUs
-constexpr long long D2_MAX_WS_FLOATS = 12ll << 20;               // workspace bound: 48 MB
 static_assert(D2_ROW >= D2_EX && D2_ROW % 32 == 8 && D2_XS % 32 == 2, "bank maps");
 static_assert(D2_TX % 4 == 0, "an MFMA step takes 4 pixels along W");
 
@@ -67,10 +64,8 @@ struct D2Regs {
 template <int NT, int COB>
 __device__ __forceinline__ void d2_load(const D2Args& a, long long br, int co0, int ci0, int tid, D2Regs<NT, COB>& r) {
   using R = D2Regs<NT, COB>;
-  const int bx = (int)(br % a.nbx);
-  br /= a.nbx;
-  const int by = (int)(br % a.nby);
-  const int b = (int)(br / a.nby);
+  int b, by, bx;
+  dv_brick_decode2(br, a.nby, a.nbx, b, by, bx);
   const int oy0 = by * D2_TY, ox0 = bx * D2_TX;
   const int Hg = 2 * a.H, Wg = 2 * a.W;
   const size_t xplane = (size_t)a.H * a.W, gplane = (size_t)Hg * Wg;
@@ -123,7 +118,8 @@ __global__ __launch_bounds__(64 * COB) void deconv2d_k4_wgrad_kernel(D2Args a) {
 #pragma unroll
   for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const float* ard = hs + wave * D2_HS + (li >> 2) * D2_ROW + (li & 3) + 2 * lk;     // tap (ty, tx) = (li >> 2, li & 3)
   const float* brd = xs + li * D2_XS + lk;
 
@@ -168,7 +164,7 @@ struct D2Plan {
 
 bool d2_valid(int B, int Ci, int H, int W, int Co) {
   return B > 0 && Ci > 0 && H > 0 && W > 0 && Co > 0 && (long long)H * W < (1ll << 28) &&
-         (long long)Ci * Co * 16 <= D2_MAX_WS_FLOATS;
+         (long long)Ci * Co * 16 <= DV_WGRAD_MAX_WS_FLOATS;
 }
 
 D2Plan d2_plan(int B, int Ci, int H, int W, int Co) {
@@ -183,13 +179,8 @@ D2Plan d2_plan(int B, int Ci, int H, int W, int Co) {
   p.nbx = (W + D2_TX - 1) / D2_TX;
   p.nbricks = (long long)B * p.nby * p.nbx;
   const long long mn = (long long)p.coblocks * p.cigroups;
-  long long s = (D2_TARGET_BLOCKS + mn - 1) / mn;
-  const long long cap = D2_MAX_WS_FLOATS / ((long long)Ci * Co * 16);
-  if (s > cap) s = cap;
-  if (s > p.nbricks / 2) s = p.nbricks / 2;               // at least two bricks per split
-  if (s > 65535) s = 65535;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  // at least two bricks per split
+  p.splits = dv_wgrad_splits((D2_TARGET_BLOCKS + mn - 1) / mn, (long long)Ci * Co * 16, p.nbricks, 2, true);
   return p;
 }
 
@@ -236,8 +227,5 @@ extern "C" int dv_deconv2d_k4s2_wgrad_f32(const float* x, const float* g, float*
   const dim3 grid((unsigned)p.coblocks, (unsigned)p.cigroups, (unsigned)p.splits);
   hipStream_t s = (hipStream_t)stream;
   d2_launch(p.nt, p.cob, grid, s, a);
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum_quartered(workspace, dw, (long long)Ci * Co * 16, p.splits, s);
-  return dv_launch_status();
+  return dv_splitk_finish(workspace, dw, (long long)Ci * Co * 16, p.splits, s, true);
 }

@@ -26,8 +26,6 @@ namespace {
 // 2 = the persistent kernel wherever it takes the shape
 std::atomic<int> g_deconv_impl_pin{0};
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kTD = 2, kTH = 2, kMTX = 2, kNT = 2;
 constexpr int kTW = kMTX * 16;
 constexpr int kCOUT = kNT * 16;

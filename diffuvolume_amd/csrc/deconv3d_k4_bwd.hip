@@ -35,11 +35,9 @@
 //   deconv3d_k4_dgrad_kernel<NT = 1 | 2 | 3>   98 | 105 | 110 VGPR, 0 spilled (vector and scalar path alike), 34 560 B LDS
 //   deconv3d_k4_wgrad_kernel<MW, NW, KW>       100 - 104 VGPR (KW = 1), 196 (KW = 2), 144 (KW = 4), 64 of them the 16
 //                                              accumulator tiles; 0 spilled; 28 928 B (1 x 1 x 4) ... 62 080 B (3 x 2 x 1) LDS
-#include "dv_common.h"
+#include "wgrad_splitk.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 bool valid_shape(int B, int Ci, int D, int H, int W, int Co) {
   return B > 0 && Ci > 0 && D > 0 && H > 0 && W > 0 && Co > 0;
@@ -199,10 +197,8 @@ int launch_dgrad(const DgArgs& a, dim3 grid, bool vec, hipStream_t s) {
 constexpr int WG_TZ = 2, WG_TY = 4, WG_TX = 8, WG_P = WG_TZ * WG_TY * WG_TX;
 constexpr int WG_EY = 2 * (WG_TY - 1) + 4, WG_EXH = WG_TX + 1, WG_ROW = 2 * WG_EXH;
 constexpr int WG_TARGET_WAVES = 2048;                    // two waves per SIMD on 256 CUs, whatever the block size
-constexpr long long WG_MAX_WS_FLOATS = 12ll << 20;       // workspace bound: 48 MB
-constexpr int pad_2mod32(int n) { return n + (((2 - n % 32) % 32) + 32) % 32; }
-constexpr int WG_XS = pad_2mod32(WG_P);                          // per-channel stride of the x tile
-constexpr int WG_HS = pad_2mod32(WG_TZ * WG_EY * WG_ROW);        // per-channel stride of the g halo (one tz)
+constexpr int WG_XS = dv_pad_2mod32(WG_P);                          // per-channel stride of the x tile
+constexpr int WG_HS = dv_pad_2mod32(WG_TZ * WG_EY * WG_ROW);        // per-channel stride of the g halo (one tz)
 static_assert(WG_TX % 4 == 0, "an MFMA step takes 4 positions along W");
 
 struct WgArgs {
@@ -235,17 +231,15 @@ __global__ __launch_bounds__(64 * MW * NW * KW) void deconv3d_k4_wgrad_kernel(Wg
 #pragma unroll
   for (int t = 0; t < 16; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const size_t xplane = (size_t)a.D * a.H * a.W, gplane = (size_t)Dg * Hg * Wg;
   const float* xrd = xs + (mw * 16 + li) * WG_XS;
   const float* hrd = hs + (nw * 16 + li) * WG_HS;
 
   for (long long br = b0; br < b1; ++br) {
-    long long r = br;
-    const int bx = (int)(r % a.nbx); r /= a.nbx;
-    const int by = (int)(r % a.nby); r /= a.nby;
-    const int bz = (int)(r % a.nbz); r /= a.nbz;
-    const int b = (int)r;
+    int b, bz, by, bx;
+    dv_brick_decode3(br, a.nbz, a.nby, a.nbx, b, bz, by, bx);
     const int oz0 = bz * WG_TZ, oy0 = by * WG_TY, ox0 = bx * WG_TX;
 
     __syncthreads();                                      // the previous brick's reads are done
@@ -347,12 +341,7 @@ WgPlan wg_plan(int B, int Ci, int D, int H, int W, int Co) {
   p.nbricks = (long long)B * p.nbz * p.nby * p.nbx;
   // split K so that the grid's waves fill the device twice over, within the workspace bound
   const long long mn = 4ll * p.mtiles * p.ntiles * p.mw * p.nw * p.kw;
-  long long s = (WG_TARGET_WAVES + mn - 1) / mn;
-  const long long cap = WG_MAX_WS_FLOATS / ((long long)Ci * Co * 64);
-  if (s > cap) s = cap;
-  if (s > p.nbricks) s = p.nbricks;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  p.splits = dv_wgrad_splits((WG_TARGET_WAVES + mn - 1) / mn, (long long)Ci * Co * 64, p.nbricks, 1, false);
   return p;
 }
 
@@ -430,8 +419,5 @@ extern "C" int dv_deconv3d_k4s2_wgrad_f32(const float* x, const float* g, float*
   else if (p.mw == 2) launch_wgrad_kernel<2, 1>(a, grid, s);
   else if (p.nw == 2) launch_wgrad_kernel<1, 2>(a, grid, s);
   else launch_wgrad_kernel<1, 1>(a, grid, s);
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum(workspace, dw, (long long)Ci * Co * 64, p.splits, s);
-  return dv_launch_status();
+  return dv_splitk_finish(workspace, dw, (long long)Ci * Co * 64, p.splits, s, false);
 }

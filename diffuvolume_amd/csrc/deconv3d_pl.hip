@@ -35,7 +35,6 @@ namespace {
 // long tile lists (the result does not depend on the grid: every output is summed in the same order by whichever block)
 std::atomic<int> g_pl_max_blocks{0};
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 

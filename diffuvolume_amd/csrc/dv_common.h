@@ -6,6 +6,9 @@
 
 #define DV_WAVE 64
 
+// the accumulator (C / D operand) of the 16x16 MFMAs: four fp32 registers per lane
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 #define DV_REQUIRE_PTR(p) \
   do {                    \
     if ((p) == nullptr) return DV_ERR_NULL; \

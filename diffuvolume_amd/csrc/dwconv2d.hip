@@ -35,7 +35,6 @@ namespace {
 constexpr int THREADS = 256, WAVES = THREADS / DV_WAVE;
 constexpr int MAX_BLOCKS = 2048;                 // 256 CUs x 8 blocks: the rest of the items by the grid-stride loop
 constexpr int MAX_ITEMS = 0x7fff0000;            // the item counter is an int and steps by at most MAX_BLOCKS * WAVES
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // How one plane is cut into wave items: LX = 1 << lxlog lanes side by side (four output columns each), LY = 64 / LX row
 // bands of th rows below one another.  A function of the OUTPUT plane's size only.

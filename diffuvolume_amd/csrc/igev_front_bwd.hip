@@ -8,7 +8,7 @@
 //   dv_conv2d_fewin_wgrad_f32     weight gradient of dv_conv2d_fewin_f32: `stem_2[0]` (3 -> 32, k3, s2,
 //                                 igev_stereo_ddim.py:100-103), `cnet.conv1` (3 -> 64, k7, s2, core/extractor.py:197) and a
 //                                 plain backbone's `conv_stem`.  Images are data: there is no input gradient.
-#include "dv_common.h"
+#include "wgrad_splitk.h"
 
 namespace {
 
@@ -123,7 +123,6 @@ __global__ __launch_bounds__(1024) void instance_norm_act_bwd_kernel(const float
 constexpr int FW_TY = 8, FW_TX = 16, FW_PIX = FW_TY * FW_TX;
 constexpr int FW_COB = 16, FW_THREADS = 256, FW_MAX_CIN = 4;
 constexpr int FW_TARGET_BLOCKS = 1024;                           // four blocks per CU on 256 CUs
-constexpr long long FW_MAX_WS_FLOATS = 12ll << 20;               // workspace bound: 48 MB
 
 struct FwArgs {
   const float* x;     // [B, Cin, H, W]
@@ -153,14 +152,12 @@ __global__ __launch_bounds__(FW_THREADS) void conv2d_fewin_wgrad_kernel(FwArgs a
 #pragma unroll
   for (int n = 0; n < FW_COB; ++n) acc[n] = 0.f;
 
-  const long long b0 = a.nbricks * split / a.splits, b1 = a.nbricks * (split + 1) / a.splits;
+  long long b0, b1;
+  dv_split_range(a.nbricks, split, a.splits, b0, b1);
   const size_t xplane = (size_t)a.H * a.W, gplane = (size_t)a.Ho * a.Wo;
   for (long long br = b0; br < b1; ++br) {
-    long long r = br;
-    const int bx = (int)(r % a.nbx);
-    r /= a.nbx;
-    const int by = (int)(r % a.nby);
-    const int b = (int)(r / a.nby);
+    int b, by, bx;
+    dv_brick_decode2(br, a.nby, a.nbx, b, by, bx);
     const int oy0 = by * FW_TY, ox0 = bx * FW_TX;
     __syncthreads();                                             // the previous brick's reads are done
     for (int i = tid; i < a.Cin * IY * IX; i += FW_THREADS) {
@@ -212,7 +209,7 @@ struct FwPlan {
 bool fw_valid(int B, int Cin, int H, int W, int Cout, int k, int stride) {
   return B > 0 && Cin > 0 && Cin <= FW_MAX_CIN && H > 0 && W > 0 && Cout > 0 && (k == 3 || k == 5 || k == 7) &&
          (stride == 1 || stride == 2) && (long long)H * W < (1ll << 28) && (long long)B * H * W < (1ll << 40) &&
-         (long long)Cout * Cin * k * k <= FW_MAX_WS_FLOATS && (Cout + FW_COB - 1) / FW_COB <= 65535;
+         (long long)Cout * Cin * k * k <= DV_WGRAD_MAX_WS_FLOATS && (Cout + FW_COB - 1) / FW_COB <= 65535;
 }
 
 FwPlan fw_plan(int B, int Cin, int H, int W, int Cout, int k, int stride) {
@@ -223,13 +220,9 @@ FwPlan fw_plan(int B, int Cin, int H, int W, int Cout, int k, int stride) {
   p.nby = (p.Ho + FW_TY - 1) / FW_TY;
   p.nbx = (p.Wo + FW_TX - 1) / FW_TX;
   p.nbricks = (long long)B * p.nby * p.nbx;
-  long long s = (FW_TARGET_BLOCKS + p.cogroups - 1) / p.cogroups;
-  const long long cap = FW_MAX_WS_FLOATS / ((long long)Cout * Cin * k * k);
-  if (s > cap) s = cap;
-  if (s > p.nbricks / 2) s = p.nbricks / 2;                      // at least two bricks per split
-  if (s > 65535) s = 65535;
-  if (s < 1) s = 1;
-  p.splits = (int)s;
+  // at least two bricks per split; the split index is grid.y
+  p.splits = dv_wgrad_splits((FW_TARGET_BLOCKS + p.cogroups - 1) / p.cogroups, (long long)Cout * Cin * k * k, p.nbricks, 2,
+                             true);
   return p;
 }
 
@@ -281,8 +274,5 @@ extern "C" int dv_conv2d_fewin_wgrad_f32(const float* x, const float* g, float* 
   else if (stride == 1) DV_FW(7, 1);
   else DV_FW(7, 2);
 #undef DV_FW
-  const int rc = dv_launch_status();
-  if (rc != DV_OK) return rc;
-  dv_splitk_sum_quartered(workspace, dw, (long long)Cout * Cin * k * k, p.splits, s);
-  return dv_launch_status();
+  return dv_splitk_finish(workspace, dw, (long long)Cout * Cin * k * k, p.splits, s, true);
 }

@@ -77,7 +77,6 @@ __global__ __launch_bounds__(256) void patch_volume_kernel(const float* __restri
 // ---- fast path ----------------------------------------------------------------------------------------------------
 constexpr int FIW = TXB + 16;        // staged input row: x0 - 8 .. x0 + 136 (tile at column 8; the outer quads are slack)
 constexpr int FMW = TXB + 8;         // first-stencil row: x0 - 4 .. x0 + 132 (tile at column 4)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int DL>
 __global__ __launch_bounds__(256) void patch_volume_vec_kernel(const float* __restrict__ in, const float* __restrict__ w1,

@@ -34,7 +34,6 @@ constexpr int FMW = TXB + 8;         // mid / dmid row in LDS: image columns x0 
 constexpr int IQ = FIW / 4, MQ = FMW / 4, OQ = TXB / 4;
 constexpr int NSUM = 18;             // dw1[0..9), dw2[0..9) of one group
 constexpr int THREADS = 256, WAVES = THREADS / DV_WAVE;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PatchGeo {
   int gx, gy;

@@ -12,7 +12,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PW_KS = 8;          // k-steps of 4 input channels: Cin <= 32
 constexpr int PW_MT = 4;          // 16-pixel M-tiles per block
 

@@ -23,8 +23,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int C = 128, HEADS = 16, HD = 8, TOK = 64, F3 = 3 * C;
 constexpr int LDW = 130;                        // w_s[row][k], as the forward
 constexpr int GH2 = 2, GF2 = 3 * GH2 * HD;      // 48 qkv features per group

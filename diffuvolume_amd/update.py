@@ -18,7 +18,7 @@ on entry.  The motion features' channel 127 carries the float32 ``disp`` unround
 
 Training (``module.train()`` with gradients enabled): ``BasicMultiUpdateBlock.forward`` takes the differentiable route of
 ``train2d`` -- the same forward kernels with ReLU / sigmoid / tanh fused, one ``train2d.ConvGRUFn`` per ConvGRU (gate
-arithmetic and its backward on csrc/conv2d_wgrad_cat.hip's elementwise kernels), weight gradients on
+arithmetic and its backward on csrc/gru_gates.hip's elementwise kernels), weight gradients on
 ``dv_conv2d_wgrad_cat_f32`` over the virtual concatenations, input gradients on the forward kernels with flipped weights
 packed once per weight key (the ``plans("train")`` slot).  ``convd1`` (7x7, one input channel) runs through autograd
 there (``train2d.Conv1InFn``) so that it learns although ``disp`` is detached; ``pool2x`` / ``interp`` keep their

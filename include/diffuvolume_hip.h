@@ -669,8 +669,8 @@ size_t dv_conv2d_wgrad_cat_workspace_floats(const int* channels, int n_inputs, i
 int dv_conv2d_wgrad_cat_f32(const float* const* inputs, const int* channels, int n_inputs, const float* g, float* dw,
                             float* workspace, int B, int H, int W, int Cout, int k, dv_stream_t stream);
 
-/* ConvGRU gate arithmetic of the training route (update.py:36-39), elementwise over n floats (float4 bodies on 16-byte
- * aligned pointers, scalar otherwise):
+/* ConvGRU gate arithmetic of the training route (update.py:36-39; csrc/gru_gates.hip), elementwise over n floats (float4
+ * bodies on 16-byte aligned pointers, scalar otherwise):
  *   dv_gru_reset_mul_f32        rh = r * h
  *   dv_gru_blend_f32            out = h + z * (q - h)   -- (1 - z) h + z q in the form, and with the rounding, of
  *                               dv_conv2d_gated_f32's blend epilogue: the training forward equals the eval forward's bits
@@ -704,8 +704,8 @@ size_t dv_conv2d_wgrad_cat_f16_workspace_floats(const int* channels, int n_input
 int dv_conv2d_wgrad_cat_f16(const float* const* inputs, const int* channels, int n_inputs, const float* g, float* dw,
                             float* workspace, int B, int H, int W, int Cout, int k, dv_stream_t stream);
 
-/* ConvGRU gate arithmetic of the training forward with the rounding points of dv_conv2d_f16_cat's epilogues (every
- * result rounded to fp16, the operands taken as they are: fp16-exact on the route):
+/* ConvGRU gate arithmetic of the training forward (csrc/gru_gates.hip) with the rounding points of dv_conv2d_f16_cat's
+ * epilogues (every result rounded to fp16, the operands taken as they are: fp16-exact on the route):
  *   dv_gru_reset_mul_f16   rh = r16(r * h)
  *   dv_gru_blend_f16       out = r16(r16(r16(1 - z) * h) + r16(z * q))
  * The backward of both stays on dv_gru_gates_bwd_*_f32. */
