@@ -61,6 +61,13 @@ KNOBS = {
                        "train2d and the fused kernels of csrc/bn3d_act.hip, and F.interpolate(bilinear, align_corners=True) "
                        "on the inference kernel with the atomics-free backward of csrc/resize_bwd.hip, so that every "
                        "gradient repeats bit for bit; torch = the nn.Module calls (MIOpen, ATen's atomic resize backward)"),
+    "DV_TRAIN_LOSS": ("hip", "train_loss.route() on every call of the model_loss_* functions and of sequence_loss",
+                      "torch = the reference's expression for every argument (est[mask], gt[mask] and a mean per prediction: "
+                      "a nonzero with a host synchronisation, index tensors and gathered copies kept for the backward) "
+                      "instead of the fused forward and backward of csrc/masked_loss.hip for float32 GPU tensors in one "
+                      "shape (gt and the mask read once for all predictions, loss and gradients repeat bit for bit, "
+                      "sequence_loss reads its metrics in one copy).  Anything else (CPU, float64, broadcasting shapes, a gt "
+                      "that requires a gradient) is the torch expression on either value (A/B runs, tests)"),
     "DV_IGEV_OVERLAP": ("1", "update.BasicMultiUpdateBlock.OVERLAP at import",
                         "0 = the motion encoder on the main stream instead of a side stream (same bits)"),
     "DV_IGEV_GRAPH": ("0", "igev_loop.IGEVDiffusionLoop.use_graph at import",

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 from pathlib import Path
 
 import torch  # noqa: F401  (must precede the dlopen below)
@@ -213,6 +213,11 @@ VOLUME_TRAIN_SIGNATURES = {
     "dv_dwconv3x3_bwd_workspace_floats": (c_size_t, [I, I, I, I, I], SIZE_ONLY),
     "dv_dwconv3x3_bwd_f32": (c_int, [P, P, P, P, P, P, I, I, I, I, I, P],
                              held_by("test_gpu_dwconv.py::test_dwconv_abi_offset_views_bounds_and_refusals")),
+    "dv_masked_loss_workspace_floats": (c_size_t, [I, c_longlong], SIZE_ONLY),
+    "dv_masked_loss_fwd_f32": (c_int, [P, P, P, P, P, I, c_float, I, c_longlong, I, P, P, P, P],
+                               held_by("test_gpu_loss_train.py::test_masked_loss_abi_offset_views_bounds_and_refusals")),
+    "dv_masked_loss_bwd_f32": (c_int, [P, P, P, P, P, I, c_float, P, P, P, I, c_longlong, P],
+                               held_by("test_gpu_loss_train.py::test_masked_loss_abi_offset_views_bounds_and_refusals")),
 }
 
 

@@ -1,7 +1,13 @@
 """Training losses of the SceneFlow models (SceneFlow/models/loss.py) and of the KITTI12 model (KITTI12/models/loss.py,
 ``model_loss_kitti12``), importable from the package so that the reference's ``main.py`` scripts can take them from here:
 a weighted sum of smooth-L1 (L1 for the test loss) terms over the pixels selected by ``mask``, one weight per prediction
-(``zip`` stops at the shorter of the two lists)."""
+(``zip`` stops at the shorter of the two lists), and IGEV's ``sequence_loss`` (KITTI15/train_stereo.py:33-62).
+
+The expressions below are the reference's, and they are what runs for CPU tensors, float64, shapes that broadcast, a ground
+truth that requires a gradient, and under ``DV_TRAIN_LOSS=torch``.  Under ``DV_TRAIN_LOSS=hip`` float32 tensors on the GPU in
+one common shape go to the fused forward and backward of ``train_loss`` (csrc/masked_loss.hip) instead: no ``nonzero`` and
+host synchronisation per prediction, no index tensors kept for the backward, loss and gradients that repeat bit for bit.
+The knob's default and the measurements behind it are in DESIGN.md, "The losses in training"."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -9,8 +15,16 @@ from typing import Sequence
 import torch
 import torch.nn.functional as F
 
+from . import train_loss
+
+_KIND = {F.smooth_l1_loss: "smooth_l1", F.l1_loss: "l1"}
+
 
 def _weighted(disp_ests: Sequence[torch.Tensor], disp_gt: torch.Tensor, mask: torch.Tensor, weights, fn):
+    if train_loss.route() == "hip":
+        ests = [est for est, _ in zip(disp_ests, weights)]
+        if train_loss.fusable(ests, disp_gt, mask):
+            return train_loss.masked_loss_train(ests, disp_gt, mask, weights, _KIND[fn])
     return sum(w * fn(est[mask], disp_gt[mask], reduction="mean") for est, w in zip(disp_ests, weights))
 
 
@@ -41,6 +55,8 @@ def sequence_loss(disp_preds, disp_init_pred, disp_gt, valid, loss_gamma: float 
     ``disp_gt`` [B,1,H,W], ``valid`` [B,H,W].  (A single prediction gets weight 1: the reference divides by zero there.)"""
     n = len(disp_preds)
     assert n >= 1
+    if train_loss.route() == "hip" and train_loss.sequence_fusable(disp_preds, disp_init_pred, disp_gt, valid):
+        return train_loss.sequence_loss_train(disp_preds, disp_init_pred, disp_gt, valid, loss_gamma, max_disp)
     mag = torch.sum(disp_gt ** 2, dim=1).sqrt()
     valid = ((valid >= 0.5) & (mag < max_disp)).unsqueeze(1)
     assert valid.shape == disp_gt.shape, [valid.shape, disp_gt.shape]

@@ -427,3 +427,21 @@ def igev_sequence_loss_inputs(seed: int, b: int = 2, h: int = 16, w: int = 24, n
     preds = [(gt + torch.randn(b, 1, h, w, generator=g) * (3.0 / (i + 1))).to(dtype) for i in range(n)]
     init = (gt + torch.randn(b, 1, h, w, generator=g) * 1.5).to(dtype)
     return preds, init, gt.to(dtype), valid
+
+
+LOSS_TRAIN_CASE = dict(seed=83, b=2, h=16, w=24, k=6)
+
+
+def loss_train_inputs(seed: int, b: int = 2, h: int = 16, w: int = 24, k: int = 6, dtype=torch.float32):
+    """Seeded arguments of the ``model_loss_*`` functions: k predictions [B,H,W] around a ground truth with pixels at 0 (no
+    ground truth) and beyond 192, the mask ``(gt < 192) & (gt > 0)`` of the training scripts, errors on both sides of
+    smooth-L1's knee, and prediction 0 equal to the ground truth at every 7th pixel (d == 0 exactly) -> (preds, gt, mask)."""
+    g = _gen(seed, "loss_train")
+    gt = torch.rand(b, h, w, generator=g) * 180 + 1
+    bad = torch.rand(b, h, w, generator=g)
+    gt[bad < 0.1] = 0.0
+    gt[bad > 0.9] = 200.0
+    preds = [gt + torch.randn(b, h, w, generator=g) * (2.5 / (i + 1)) for i in range(k)]
+    preds[0].view(-1)[::7] = gt.view(-1)[::7]
+    mask = (gt < 192) & (gt > 0)
+    return [p.to(dtype) for p in preds], gt.to(dtype), mask

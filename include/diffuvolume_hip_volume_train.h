@@ -4,7 +4,8 @@
  * + skip + activation of the ACV and PCW aggregation stacks in training, forward and backward, the backward of the
  * patch stencils of ACVNet_DDIM's attention branch (dv_patch_volume_runs_f32), the backward of the hourglass's
  * bottleneck window attention (dv_window_attn3d_f32), the backward of the align_corners=True bilinear resize
- * (dv_resize_bilinear_ac_f32), and the depthwise 3x3 convolution of IGEV's MobileNetV2 backbone, forward and backward.
+ * (dv_resize_bilinear_ac_f32), the depthwise 3x3 convolution of IGEV's MobileNetV2 backbone, forward and backward, and the
+ * masked training losses of the three models, forward and backward.
  *
  * Bound by `_lib.VOLUME_TRAIN_SIGNATURES`, where every entry also carries the decision about its pointer and bounds
  * contract ("size only" or the GPU test that holds it); tests/test_volume_train_host.py reads that table.  A later
@@ -244,6 +245,54 @@ int dv_dwconv3x3_f32(const float* x, const float* w, const float* scale, const f
 size_t dv_dwconv3x3_bwd_workspace_floats(int B, int C, int H, int W, int stride);
 int dv_dwconv3x3_bwd_f32(const float* x, const float* w, const float* dy, float* dx, float* dw, float* workspace, int B,
                          int C, int H, int W, int stride, dv_stream_t stream);
+
+/* ---- the masked training losses, forward and backward -------------------------------------------------------------------
+ * The weighted sum of masked means every training script of the three models ends in (SceneFlow/models/loss.py,
+ * KITTI12/models/loss.py: smooth-L1 / L1 over est[mask]; KITTI15/train_stereo.py:33-62: sequence_loss), for K predictions
+ * in one pass instead of one boolean gather per prediction:
+ *   pred_k, gt [n] float32;  d = pred_k[i] - gt[i];  g_k = |d| (DV_LOSS_L1) or, DV_LOSS_SMOOTH_L1 with beta 1,
+ *   0.5 d^2 for |d| < 1 and |d| - 0.5 otherwise
+ *   selected(i): DV_MASK_U8        mask is n bytes, non-zero selects (a bool tensor)
+ *                DV_MASK_VALID_F32 mask is n floats `valid`: valid[i] >= 0.5f && sqrtf(gt[i] * gt[i]) < max_disp, in float32
+ *   sum_k = sum_{selected} g_k,  count = #selected,   loss = sum_k w_k * sum_k / count
+ * `preds`, `weights`, `kinds` (and `dpreds`) are HOST arrays of K entries; preds[k] / dpreds[k] are device pointers.  They are
+ * read during the call only (they travel to the kernels by value).  1 <= K <= DV_MASKED_LOSS_MAX_K; more predictions are
+ * several calls, whose sums do not depend on each other.
+ *
+ * Forward: one grid-stride launch of at most DV_MASKED_LOSS_MAX_BLOCKS blocks of 256 threads, a thread taking quads of four
+ * consecutive elements, leaves one partial per block and figure, in double, in `workspace`
+ * (dv_masked_loss_workspace_floats floats = 2 * blocks * (K + 6), on an 8-byte line; 0 for arguments the forward refuses);
+ * a one-block launch adds the partials in a fixed order in double and writes
+ *   stats [K + 6] double: sum_0 .. sum_{K-1}, count, and for prediction `metric_pred` (-1: none, the four are 0)
+ *                         sum |d|, #(|d| < 1), #(|d| < 3), #(|d| < 5) over the selected pixels, then 1.0 if a selected gt is
+ *                         infinite and 0.0 otherwise
+ *   loss  [1] float32:    the expression above, combined in double and rounded once; NaN for count == 0 (the mean of an
+ *                         empty selection) and when a selected d is NaN.
+ * Backward: one launch writes every element of every dpreds[k] != NULL exactly once:
+ *   dpred_k[i] = gout[0] * w_k / count * g_k'(d) at selected pixels, g' = sign(d) with sign(0) = 0 for L1, d for |d| < 1
+ *   and sign(d) otherwise for smooth-L1, NaN for a NaN d;  0 at unselected pixels BY SELECTION, whatever pred and gt hold
+ *   there (NaN, Inf);  all 0 for count == 0.  `gout` is a DEVICE float (the incoming gradient of the loss, e.g. a
+ *   GradScaler's scale), `stats` the forward's.  dpreds[k] == NULL: that prediction needs no gradient and is skipped;
+ *   all NULL: DV_ERR_NULL.  dpreds must not overlap an input.
+ * No atomics in any launch: the same call gives the same bits.  16-byte loads and stores (the mask bytes four at a time) when
+ * every tensor operand lies on a 16-byte line (a byte mask: a 4-byte line), element accesses otherwise and at the tail, with
+ * the same assignment of elements to threads and the same order of additions: the same bits.
+ * Refused before anything touches the device: a NULL pointer (an entry of preds included) DV_ERR_NULL; n <= 0, K outside
+ * 1..DV_MASKED_LOSS_MAX_K or metric_pred outside -1..K-1 DV_ERR_SHAPE; an unknown kind or mask mode, a NaN max_disp with
+ * DV_MASK_VALID_F32 DV_ERR_UNSUPPORTED; workspace or stats off an 8-byte line DV_ERR_ALIGN. */
+#define DV_MASKED_LOSS_MAX_K 24
+#define DV_MASKED_LOSS_MAX_BLOCKS 1024
+#define DV_LOSS_L1 0
+#define DV_LOSS_SMOOTH_L1 1
+#define DV_MASK_U8 0
+#define DV_MASK_VALID_F32 1
+size_t dv_masked_loss_workspace_floats(int K, long long n);
+int dv_masked_loss_fwd_f32(const float* const* preds, const double* weights, const int* kinds, const float* gt,
+                           const void* mask, int mask_mode, float max_disp, int K, long long n, int metric_pred,
+                           float* workspace, double* stats, float* loss, dv_stream_t stream);
+int dv_masked_loss_bwd_f32(const float* const* preds, const double* weights, const int* kinds, const float* gt,
+                           const void* mask, int mask_mode, float max_disp, const double* stats, const float* gout,
+                           float* const* dpreds, int K, long long n, dv_stream_t stream);
 
 #ifdef __cplusplus
 }
