@@ -6,8 +6,9 @@ kernel reports an error the call raises.  ``import torch`` happens first so the
 library resolves libamdhip64 against the HIP runtime PyTorch already loaded
 (one runtime, one set of streams).
 
-What every training route needs around an entry is here once: ``check_f32`` (a float32 tensor on the GPU),
-``launch(name, device, *args)`` (the call on PyTorch's current stream of that device, its code checked) and
+What every route needs around an entry is here once: ``check_f32`` (a float32 tensor on the GPU),
+``launch(name, device, *args)`` (the call on PyTorch's current stream of that device, its code checked),
+``timed_launch(tag, flops, nbytes, name, device, *args)`` (the same call under the kernel timer of profiling.py) and
 ``workspace(name, device, *dims)`` (the float32 scratch a ``*_workspace_floats`` entry sizes; None for 0).
 """
 from __future__ import annotations
@@ -18,6 +19,8 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_lon
 from pathlib import Path
 
 import torch  # noqa: F401  (must precede the dlopen below)
+
+from .profiling import timed
 
 # DV_LIB_PATH: load another build of the same ABI (A/B of compiler flags / kernel variants); default = the in-tree .so
 _LIB_PATH = Path(os.environ.get("DV_LIB_PATH") or Path(__file__).resolve().parent / "libdiffuvolume_hip.so")
@@ -264,11 +267,11 @@ def ptr(t) -> int:
 
 
 def check_f32(t, name: str) -> None:
-    """The training routes' tensor check: a float32 tensor on the GPU, or an error that names it."""
+    """Every route's tensor check: a float32 tensor on the GPU, or an error that names it."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
     if not t.is_cuda:
-        raise DiffuVolumeError(f"{name} is on {t.device}: training runs on the MI355X (no CPU fallback)")
+        raise DiffuVolumeError(f"{name} is on {t.device}: this path only runs on the MI355X (HIP kernels, no CPU fallback)")
     if t.dtype != torch.float32:
         raise TypeError(f"{name} must be float32, got {t.dtype}")
 
@@ -277,6 +280,14 @@ def launch(name: str, device, *args) -> None:
     """Call the entry ``name`` with ``args`` and PyTorch's current stream of ``device``; raise on its error code."""
     with torch.cuda.device(device):
         check(getattr(load(), name)(*args, stream_ptr()), name)
+
+
+def timed_launch(tag: str, flops: float, nbytes: float, name: str, device, *args, issued: float = 0.0, valu: float = 0.0) -> None:
+    """``launch`` as one record of the kernel timer (``profiling.timed``: what ``tag``, ``flops``, ``nbytes``, ``issued`` and
+    ``valu`` mean).  The device is entered around the timer, whose events go to the current device's stream."""
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        timed(tag, flops, nbytes, lambda: check(fn(*args, stream_ptr()), name), issued, valu)
 
 
 def workspace(name: str, device, *dims):

@@ -98,16 +98,13 @@ def noise_prepare(time_embedding, x_t: torch.Tensor, t: Optional[torch.Tensor], 
     b, c, h, w = x_t.shape
     if shift is None:
         shift = time_embedding.shift(t).float().contiguous()
-    lib = _lib.load()
     x_t = x_t.contiguous()
     n01 = torch.empty_like(x_t)
     if x_t.dtype == torch.float32:
-        _lib.check(lib.dv_noise_prepare_f32(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), b, c, h * w,
-                                            _lib.stream_ptr()), "dv_noise_prepare_f32")
+        _lib.launch("dv_noise_prepare_f32", x_t.device, x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), b, c, h * w)
         return n01, n01
     n01f = torch.empty(x_t.shape, dtype=torch.float32, device=x_t.device)
-    _lib.check(lib.dv_noise_prepare_f64(x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), n01f.data_ptr(),
-                                        b, c, h * w, _lib.stream_ptr()), "dv_noise_prepare_f64")
+    _lib.launch("dv_noise_prepare_f64", x_t.device, x_t.data_ptr(), shift.data_ptr(), n01.data_ptr(), n01f.data_ptr(), b, c, h * w)
     return n01, n01f
 
 
@@ -124,11 +121,10 @@ def ddim_update(disp, used, n01, eps, fill, mask, ens, coef: _lib.DvDdimCoef, *,
     f32 = n01.dtype == torch.float32
     eps32 = eps if (eps is not None and eps.dtype == torch.float32) else None
     eps64 = eps if (eps is not None and eps.dtype == torch.float64) else None
-    _lib.check(_lib.load().dv_ddim_step(disp.data_ptr(), _lib.ptr(unc), used.data_ptr(), _lib.ptr(coords0),
-                                        n01.data_ptr() if f32 else 0, 0 if f32 else n01.data_ptr(),
-                                        _lib.ptr(eps32), _lib.ptr(eps64), _lib.ptr(fill), mask.data_ptr(),
-                                        x_start.data_ptr(), _lib.ptr(pred_noise), _lib.ptr(x_next), _lib.ptr(ens),
-                                        b, c, h, w, ctypes.byref(coef), _lib.stream_ptr()), "dv_ddim_step")
+    _lib.launch("dv_ddim_step", dev, disp.data_ptr(), _lib.ptr(unc), used.data_ptr(), _lib.ptr(coords0),
+                n01.data_ptr() if f32 else 0, 0 if f32 else n01.data_ptr(), _lib.ptr(eps32), _lib.ptr(eps64), _lib.ptr(fill),
+                mask.data_ptr(), x_start.data_ptr(), _lib.ptr(pred_noise), _lib.ptr(x_next), _lib.ptr(ens), b, c, h, w,
+                ctypes.byref(coef))
     return x_start, x_next, pred_noise
 
 
@@ -137,9 +133,7 @@ def encode_two_hot(disp: torch.Tensor, bins: int) -> torch.Tensor:
     (acv_ddim.py:403-419)."""
     b, h, w = disp.shape[0], disp.shape[-2], disp.shape[-1]
     x = torch.empty((b, bins, h, w), dtype=torch.float32, device=disp.device)
-    with torch.cuda.device(disp.device):
-        _lib.check(_lib.load().dv_encode_two_hot_f32(disp.data_ptr(), x.data_ptr(), b, bins, h * w, _lib.stream_ptr()),
-                   "dv_encode_two_hot_f32")
+    _lib.launch("dv_encode_two_hot_f32", disp.device, disp.data_ptr(), x.data_ptr(), b, bins, h * w)
     return x
 
 

@@ -24,8 +24,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _env, _lib
-from .profiling import timed
-from .submodule import _dev_f32, _wants_grad
+from .plans import _dev_f32, pack
+from .submodule import _wants_grad
 
 route = functools.partial(_env.route, "DV_TRAIN_LOOKUP")     # what the training route of the lookup and the correlation runs on
 
@@ -58,14 +58,11 @@ class AllPairsCorrFn(torch.autograd.Function):
         if d1 is None and d2 is None:
             return None, None
         n = (d1 is not None) + (d2 is not None)
-        lib = _lib.load()
-        with torch.cuda.device(g0.device):
-            timed("allpairs_corr_bwd", 2.0 * n * B * H * W1 * W2 * C,
-                  4.0 * (n * g0.numel() + (f2.numel() + f1.numel() if d1 is not None else 0)
-                         + (f1.numel() + f2.numel() if d2 is not None else 0)),
-                  lambda: _lib.check(lib.dv_allpairs_corr_bwd_f32(g0.data_ptr(), f1.data_ptr(), f2.data_ptr(), _lib.ptr(d1),
-                                                                  _lib.ptr(d2), B, C, H, W1, W2, _lib.stream_ptr()),
-                                     "dv_allpairs_corr_bwd_f32"), issued=2.0 * n * B * H * W1 * W2 * C)
+        _lib.timed_launch("allpairs_corr_bwd", 2.0 * n * B * H * W1 * W2 * C,
+                          4.0 * (n * g0.numel() + (f2.numel() + f1.numel() if d1 is not None else 0)
+                                 + (f1.numel() + f2.numel() if d2 is not None else 0)),
+                          "dv_allpairs_corr_bwd_f32", g0.device, g0.data_ptr(), f1.data_ptr(), f2.data_ptr(), _lib.ptr(d1),
+                          _lib.ptr(d2), B, C, H, W1, W2, issued=2.0 * n * B * H * W1 * W2 * C)
         return d1, d2
 
 
@@ -89,12 +86,9 @@ class GeoLookupFn(torch.autograd.Function):
         if dgeo is not None or dcorr0 is not None:
             nbytes = 4.0 * (g.numel() + (dgeo.numel() + noisy.numel() if dgeo is not None else 0)
                             + (dcorr0.numel() if dcorr0 is not None else 0))
-            lib = _lib.load()
-            with torch.cuda.device(g.device):
-                timed("geo_filter_lookup_bwd", 0.0, nbytes,
-                      lambda: _lib.check(lib.dv_geo_filter_lookup_bwd_f32(
-                          g.data_ptr(), disp.data_ptr(), coords.data_ptr(), noisy.data_ptr(), _lib.ptr(dgeo),
-                          _lib.ptr(dcorr0), b, c, d, h, w, w2, radius, _lib.stream_ptr()), "dv_geo_filter_lookup_bwd_f32"))
+            _lib.timed_launch("geo_filter_lookup_bwd", 0.0, nbytes, "dv_geo_filter_lookup_bwd_f32", g.device, g.data_ptr(),
+                              disp.data_ptr(), coords.data_ptr(), noisy.data_ptr(), _lib.ptr(dgeo), _lib.ptr(dcorr0),
+                              b, c, d, h, w, w2, radius)
         return None, dgeo, dcorr0, None, None, None
 
 
@@ -152,12 +146,7 @@ def pack_lookup_conv1x1(weight: torch.Tensor, channel: int = 8) -> torch.Tensor:
     w = _dev_f32(weight.detach().reshape(weight.shape[0], -1), "weight")
     if tuple(w.shape) != (64, 2 * (9 * channel + 9)):
         raise _lib.DiffuVolumeError(f"fused lookup + 1x1 convolution: weight [64, {2 * (9 * channel + 9)}], got {tuple(w.shape)}")
-    lib = _lib.load()
-    out = torch.empty(lib.dv_geo_lookup_conv1x1_packed_floats(channel), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(lib.dv_geo_lookup_conv1x1_pack_weights_f32(w.data_ptr(), out.data_ptr(), channel, _lib.stream_ptr()),
-                   "dv_geo_lookup_conv1x1_pack_weights_f32")
-    return out
+    return pack("dv_geo_lookup_conv1x1_packed_floats", "dv_geo_lookup_conv1x1_pack_weights_f32", w, channel)
 
 
 class Combined_Geo_Encoding_Volume:
@@ -216,13 +205,9 @@ class Combined_Geo_Encoding_Volume:
         b, c, d, h, w = geo.shape
         nch = 2 * (c * (2 * radius + 1) + (2 * radius + 1))
         out = torch.empty((b, nch, h, w), dtype=torch.float32, device=disp.device)
-        lib = _lib.load()
-        with torch.cuda.device(disp.device):
-            timed("geo_filter_lookup", 0.0, 4.0 * (out.numel() + noisy.numel()),
-                  lambda: _lib.check(lib.dv_geo_filter_lookup_f32(
-                      geo.data_ptr(), corr0.data_ptr(), corr1.data_ptr(), disp.data_ptr(),
-                      coords.data_ptr(), noisy.data_ptr(), out.data_ptr(), b, c, d, h, w, corr0.shape[-1],
-                      radius, _lib.stream_ptr()), "dv_geo_filter_lookup_f32"))
+        _lib.timed_launch("geo_filter_lookup", 0.0, 4.0 * (out.numel() + noisy.numel()), "dv_geo_filter_lookup_f32", disp.device,
+                          geo.data_ptr(), corr0.data_ptr(), corr1.data_ptr(), disp.data_ptr(), coords.data_ptr(), noisy.data_ptr(),
+                          out.data_ptr(), b, c, d, h, w, corr0.shape[-1], radius)
         return out
 
     def request(self, disp, coords, noisy) -> GeoLookupRequest:
@@ -242,15 +227,11 @@ class Combined_Geo_Encoding_Volume:
             raise RuntimeError("disp/coords must be [B,1,h,w] and noisy [B,D,h,w] for this volume")
         nch = 2 * (c * (2 * self.radius + 1) + (2 * self.radius + 1))
         out = torch.empty((b, 64, h, w), dtype=torch.float32, device=disp.device)
-        lib = _lib.load()
-        with torch.cuda.device(disp.device):
-            fl = 2.0 * out.numel() * nch
-            timed("geo_filter_lookup_conv1x1", fl, 4.0 * (out.numel() + noisy.numel()),
-                  lambda: _lib.check(lib.dv_geo_filter_lookup_conv1x1_f32(
-                      self.geo_volume.data_ptr(), self.corr0.data_ptr(), self.corr1.data_ptr(), disp.data_ptr(),
-                      coords.data_ptr(), noisy.data_ptr(), wpacked.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, c, d, h, w,
-                      self.corr0.shape[-1], self.radius, 64, act, _lib.stream_ptr()), "dv_geo_filter_lookup_conv1x1_f32"),
-                  issued=fl * 20.0 / 18.0)
+        fl = 2.0 * out.numel() * nch
+        _lib.timed_launch("geo_filter_lookup_conv1x1", fl, 4.0 * (out.numel() + noisy.numel()), "dv_geo_filter_lookup_conv1x1_f32",
+                          disp.device, self.geo_volume.data_ptr(), self.corr0.data_ptr(), self.corr1.data_ptr(), disp.data_ptr(),
+                          coords.data_ptr(), noisy.data_ptr(), wpacked.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, c, d, h, w,
+                          self.corr0.shape[-1], self.radius, 64, act, issued=fl * 20.0 / 18.0)
         return out
 
     @staticmethod
@@ -262,12 +243,9 @@ class Combined_Geo_Encoding_Volume:
         W2 = fmap2.shape[-1]
         corr0 = torch.empty((B, H, W1, W2), dtype=torch.float32, device=fmap1.device)
         corr1 = torch.empty((B, H, W1, W2 // 2), dtype=torch.float32, device=fmap1.device)
-        lib = _lib.load()
-        with torch.cuda.device(fmap1.device):
-            timed("allpairs_corr", 2.0 * B * H * W1 * W2 * C, 4.0 * (fmap1.numel() + fmap2.numel() + corr0.numel() + corr1.numel()),
-                  lambda: _lib.check(lib.dv_allpairs_corr_f32(fmap1.data_ptr(), fmap2.data_ptr(), corr0.data_ptr(),
-                                                              corr1.data_ptr(), B, C, H, W1, W2, _lib.stream_ptr()),
-                                     "dv_allpairs_corr_f32"), issued=2.0 * B * H * W1 * W2 * C)
+        _lib.timed_launch("allpairs_corr", 2.0 * B * H * W1 * W2 * C, 4.0 * (fmap1.numel() + fmap2.numel() + corr0.numel() + corr1.numel()),
+                          "dv_allpairs_corr_f32", fmap1.device, fmap1.data_ptr(), fmap2.data_ptr(), corr0.data_ptr(), corr1.data_ptr(),
+                          B, C, H, W1, W2, issued=2.0 * B * H * W1 * W2 * C)
         return corr0, corr1
 
     @staticmethod

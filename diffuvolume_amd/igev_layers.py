@@ -119,11 +119,8 @@ class _FewInPlan:
             raise RuntimeError(f"expected {self.cin} input channels, got {c}")
         out = torch.empty((b, self.cout, (h - 1) // self.stride + 1, (w - 1) // self.stride + 1), dtype=torch.float32,
                           device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dv_conv2d_fewin_f32(x.data_ptr(), self.w.data_ptr(), _lib.ptr(self.bias),
-                                                       _lib.ptr(self.scale), _lib.ptr(self.shift), out.data_ptr(), b, c, h, w,
-                                                       self.cout, self.k, self.stride, self.act, _lib.stream_ptr()),
-                       "dv_conv2d_fewin_f32")
+        _lib.launch("dv_conv2d_fewin_f32", x.device, x.data_ptr(), self.w.data_ptr(), _lib.ptr(self.bias), _lib.ptr(self.scale),
+                    _lib.ptr(self.shift), out.data_ptr(), b, c, h, w, self.cout, self.k, self.stride, self.act)
         return out
 
 
@@ -182,9 +179,7 @@ def instance_norm_act(x: torch.Tensor, act: int = ACT_NONE, eps: float = 1e-5, i
     x = _dev_f32(x, "x")
     b, c, h, w = x.shape
     out = x if inplace else torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dv_instance_norm_act_f32(x.data_ptr(), out.data_ptr(), b * c, h * w, float(eps), act,
-                                                        _lib.stream_ptr()), "dv_instance_norm_act_f32")
+    _lib.launch("dv_instance_norm_act_f32", x.device, x.data_ptr(), out.data_ptr(), b * c, h * w, float(eps), act)
     return out
 
 

@@ -31,10 +31,8 @@ def image_sums(est: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor) -> torch
     m8 = mask.to(torch.uint8).contiguous()
     b = est.shape[0]
     sums = torch.empty((b, 8), dtype=torch.float64, device=est.device)
-    with torch.cuda.device(est.device):
-        _lib.check(_lib.load().dv_masked_metrics_f32(est.data_ptr(), gt.data_ptr(), m8.data_ptr(),
-                                                     sums.data_ptr(), b, est.shape[1] * est.shape[2],
-                                                     _lib.stream_ptr()), "dv_masked_metrics_f32")
+    _lib.launch("dv_masked_metrics_f32", est.device, est.data_ptr(), gt.data_ptr(), m8.data_ptr(), sums.data_ptr(), b,
+                est.shape[1] * est.shape[2])
     return sums
 
 

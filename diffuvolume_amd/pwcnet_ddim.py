@@ -36,7 +36,6 @@ from .head import DynamicHead
 from .train_tail import regress_head
 from .train_refine import warp_corr_train
 from .train_norm import bn_act
-from .profiling import timed
 from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, refine_inputs,
                         upsample_softmax_regress)
@@ -413,9 +412,7 @@ def space_to_batch2(x: torch.Tensor) -> torch.Tensor:
     """[N,C,h,w] -> [4N,C,h/2,w/2]: sub-image (y & 1, x & 1) of item n becomes item 4n + 2(y & 1) + (x & 1) (HIP)."""
     n, c, h, w = x.shape
     out = torch.empty((4 * n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dv_space_to_batch2_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, _lib.stream_ptr()),
-                   "dv_space_to_batch2_f32")
+    _lib.launch("dv_space_to_batch2_f32", x.device, x.data_ptr(), out.data_ptr(), n, c, h, w)
     return out
 
 
@@ -424,9 +421,7 @@ def batch_to_space(x: torch.Tensor, levels: int) -> torch.Tensor:
     n, c, h, w = x.shape
     b = n >> (2 * levels)
     out = torch.empty((b, c, h << levels, w << levels), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dv_batch_to_space_f32(x.data_ptr(), out.data_ptr(), b, c, h << levels, w << levels, levels,
-                                                     _lib.stream_ptr()), "dv_batch_to_space_f32")
+    _lib.launch("dv_batch_to_space_f32", x.device, x.data_ptr(), out.data_ptr(), b, c, h << levels, w << levels, levels)
     return out
 
 
@@ -721,12 +716,9 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
         cost = cost[:, 0] if cost.dim() == 5 else cost
         b, d, h, w = cost.shape
         unc = torch.empty_like(disp)
-        lib = _lib.load()
-        timed("upsample_softmax_uncertainty", 0.0, 4.0 * (cost.numel() + 2 * disp.numel()),
-              lambda: _lib.check(lib.dv_upsample_softmax_uncertainty_f32(cost.data_ptr(), disp.data_ptr(),
-                                                                         unc.data_ptr(), b, d, h, w, 1,
-                                                                         _lib.stream_ptr()),
-                                 "dv_upsample_softmax_uncertainty_f32"))
+        _lib.timed_launch("upsample_softmax_uncertainty", 0.0, 4.0 * (cost.numel() + 2 * disp.numel()),
+                          "dv_upsample_softmax_uncertainty_f32", cost.device, cost.data_ptr(), disp.data_ptr(), unc.data_ptr(),
+                          b, d, h, w, 1)
         return unc
 
     def _step_coef(self, time, time_next, cof):

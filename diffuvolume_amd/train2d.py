@@ -46,7 +46,6 @@ convolution of its blocks (csrc/dwconv2d.hip, forward and backward).  ``conv2d_a
 convolutions: a depthwise layer reaches ``dwconv2d`` through the backbone's block classes only."""
 from __future__ import annotations
 
-import ctypes
 import functools
 from typing import Optional
 
@@ -54,8 +53,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _env, _lib
-from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan,
-                        Deconv2dK4S2Plan)
+from .plans import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan,
+                    Deconv2dK4S2Plan, cat_args)
 
 route = functools.partial(_env.route, "DV_TRAIN_CONV2D")
 
@@ -147,14 +146,13 @@ def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) 
         raise _lib.DiffuVolumeError("conv2d_cat_weight_grad: 1..4 sources with the batch and plane of the gradient")
     for t in (*sources, g):
         _lib.check_f32(t, "conv2d_cat_weight_grad operand")
-    ptrs = (ctypes.c_void_p * len(sources))(*[t.data_ptr() for t in sources])
-    chans = (ctypes.c_int * len(sources))(*[t.shape[1] for t in sources])
+    ptrs, chans, n = cat_args(sources)
     size = "dv_conv2d_wgrad_cat_f16_workspace_floats" if f16 else "dv_conv2d_wgrad_cat_workspace_floats"
-    ws = _lib.workspace(size, g.device, chans, len(sources), b, h, w, cout, k)
+    ws = _lib.workspace(size, g.device, chans, n, b, h, w, cout, k)
     if ws is None:
         raise _lib.DiffuVolumeError(f"{name} does not take k={k}, channels {list(chans)}, Cout {cout}")
     dw = torch.empty((cout, sum(chans), k, k), dtype=torch.float32, device=g.device)
-    _lib.launch(name, g.device, ptrs, chans, len(sources), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h, w, cout, k)
+    _lib.launch(name, g.device, ptrs, chans, n, g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, h, w, cout, k)
     return dw
 
 

@@ -43,7 +43,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .submodule import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan, PlanCache
+from .plans import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Conv2dF16Plan, Conv2dPairPlan, Conv2dPlan, PlanCache
 
 
 def autocast_f16() -> bool:
@@ -282,10 +282,8 @@ class BasicMotionEncoder(_Planned):
         b, _, h, w = disp.shape
         out = torch.empty((b, self.convd1.out_channels, h, w), dtype=torch.float32, device=disp.device)
         wt, bias = self.convd1.weight.contiguous(), self.convd1.bias
-        fn = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
-        with torch.cuda.device(disp.device):
-            _lib.check(getattr(_lib.load(), fn)(disp.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w,
-                                                out.shape[1], int(wt.shape[-1]), ACT_RELU, _lib.stream_ptr()), fn)
+        _lib.launch("dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32", disp.device, disp.data_ptr(), wt.data_ptr(),
+                    _lib.ptr(bias), out.data_ptr(), b, h, w, out.shape[1], int(wt.shape[-1]), ACT_RELU)
         return out
 
 
@@ -337,9 +335,7 @@ def pool2x(x):
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty((b, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dv_avg_pool3s2_f32(x.data_ptr(), out.data_ptr(), b * c, h, w, _lib.stream_ptr()),
-                   "dv_avg_pool3s2_f32")
+    _lib.launch("dv_avg_pool3s2_f32", x.device, x.data_ptr(), out.data_ptr(), b * c, h, w)
     return out
 
 
@@ -355,9 +351,7 @@ def interp(x, dest):
     b, c, h, w = x.shape
     H, W = int(dest.shape[2]), int(dest.shape[3])
     out = torch.empty((b, c, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dv_resize_bilinear_ac_f32(x.data_ptr(), out.data_ptr(), b * c, h, w, H, W,
-                                                         _lib.stream_ptr()), "dv_resize_bilinear_ac_f32")
+    _lib.launch("dv_resize_bilinear_ac_f32", x.device, x.data_ptr(), out.data_ptr(), b * c, h, w, H, W)
     return out
 
 
