@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .plans import settle_build
 
 NoiseFn = Callable[[str, Tuple[int, ...], torch.dtype], torch.Tensor]
 
@@ -147,7 +148,9 @@ class _LoopStep:
 
     def shift_rows(self, b: int) -> torch.Tensor:
         if b not in self._rows:
-            self._rows[b] = self.shift.reshape(1, -1).expand(b, -1).contiguous()
+            rows = self.shift.reshape(1, -1).expand(b, -1).contiguous()
+            settle_build(rows.device)          # kept for every later caller, whatever its stream
+            self._rows[b] = rows
         return self._rows[b]
 
 
@@ -163,6 +166,7 @@ def loop_plan(model, tables: Tables, device) -> List[_LoopStep]:
             t = torch.full((1,), time, device=device, dtype=torch.long)
             shift = model.time_embedding.shift(t).float().reshape(-1).contiguous()
             steps.append(_LoopStep(time, time_next, model._step_coef(time, time_next, model.ensemble_cof[i + 1]), shift))
+        settle_build(device)                   # the shifts are kept for every later caller, whatever its stream
         tables.loop_steps, tables.loop_key = steps, key
     return tables.loop_steps
 

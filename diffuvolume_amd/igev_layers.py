@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, train2d, train3d
+from .plans import settle_build
 from .submodule import (ACT_LEAKY, ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv2dK4S2Plan, Deconv3dPlan, _dev_f32,
                         weight_key)
 
@@ -89,6 +90,7 @@ def hip_conv2d(conv: nn.Module, x: torch.Tensor, bn: Optional[nn.BatchNorm2d] = 
                 plan = Conv2dPlan(w, _bn_tuple(bn), act=act, bias=conv.bias, stride=st, eps=bn.eps if bn is not None else 1e-5)
             else:
                 raise _lib.DiffuVolumeError(f"Conv2d on the HIP front: unsupported layer {conv}")
+        settle_build(x.device)                 # the cache is shared by every stream and thread that calls this layer
         _PLAN_CACHE[conv] = hit = (key, plan)
     plan = hit[1]
     if residual is not None:
@@ -145,7 +147,9 @@ def hip_dwconv2d(conv: nn.Conv2d, x: torch.Tensor, bn: Optional[nn.BatchNorm2d] 
     key = (act, weight_key([conv.weight] + (list(_bn_tuple(bn)) if bn is not None else [])))
     hit = _PLAN_CACHE.get(conv)
     if hit is None or hit[0] != key:
-        _PLAN_CACHE[conv] = hit = (key, _DepthwisePlan(conv.weight, bn, depthwise_stride(conv), act))
+        plan = _DepthwisePlan(conv.weight, bn, depthwise_stride(conv), act)
+        settle_build(x.device)
+        _PLAN_CACHE[conv] = hit = (key, plan)
     return hit[1](x)
 
 

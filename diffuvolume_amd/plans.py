@@ -40,7 +40,9 @@ def split_overflow_flag(device) -> torch.Tensor:
     """Device int32 the split-fp16 conv kernels raise when an activation leaves the fp16 range."""
     key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
     if key not in _OVERFLOW_FLAGS:
-        _OVERFLOW_FLAGS[key] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", key))
+        flag = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", key))
+        settle_build(flag.device)             # zeroed before a kernel on any other stream can raise it
+        _OVERFLOW_FLAGS[key] = flag
     return _OVERFLOW_FLAGS[key]
 
 
@@ -249,6 +251,19 @@ class Conv3dPlan:
         return out
 
 
+def settle_build(device=None) -> None:
+    """Wait for the stream something was just BUILT on -- packed weights, folded BatchNorm, a table -- before it is kept
+    where another stream can find it: the current stream of ``device`` (None: the current device).  The build's kernels
+    are enqueued there and nothing else orders them before a consumer on another stream -- a second thread, a replica
+    that finds the plans parked, the same caller on a later request.  Once per build, never per step.  A capturing
+    stream cannot be waited for and is left alone: builds are never captured (igev_loop.py warms up eagerly)."""
+    if not torch.cuda.is_available():
+        return
+    with torch.cuda.device(device):
+        if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream().synchronize()
+
+
 def weight_key(tensors) -> tuple:
     """Identity of a weight set: (storage address, in-place version) of every tensor -- a weight replaced through
     ``param.data = ...`` changes the address, an in-place write (``copy_``, an optimizer step) the version."""
@@ -266,7 +281,13 @@ class PlanCache:
       whole subtree when they differ;
     - ``nn.DataParallel`` re-creates its replicas on EVERY forward (SceneFlow/test_sceneflow_ddim.py:54-61, KITTI12/
       test.py), so a replica parks the plans it builds on the module it was copied from, keyed by device and slot and
-      valid for one weight key of that SOURCE (the replicas' own weights are re-broadcast from it each time)."""
+      valid for one weight key of that SOURCE (the replicas' own weights are re-broadcast from it each time).
+
+    Streams: this level carries the guarantee that plans may cross streams.  When ``plans(slot)`` or ``prepare()`` returns,
+    the stream the plans were built on has been waited for (``settle_build``, before they are stored or parked), so they
+    may be used on any stream of their device -- by another thread, or by a replica that finds them parked.  What a
+    plan builds later on first use and keeps (``_RefinePlan.plan``, the per-layer cache of igev_layers, ``ddim.loop_plan``)
+    settles the same way.  A bare plan object built outside a PlanCache belongs to the stream that built it."""
 
     @property
     def _plans(self):
@@ -293,12 +314,19 @@ class PlanCache:
                 p = parked[where][1] if where in parked and parked[where][0] == src_key else None
             if p is None:
                 p = self._build_plans(slot)
+                self._settle_build()          # before the plans are stored or parked: from here on any stream may use them
                 if src is not None:
                     parked[where] = (src_key, p)
             if "_plan_key" not in self.__dict__:
                 self.__dict__["_plan_key"] = self._weight_key()
             slots[slot] = p
         return p
+
+    def _settle_build(self):
+        """``settle_build`` on the device of the weights (a replica's weights are plain attributes: the current device)."""
+        devices = {t.device for t in itertools.chain(self.parameters(), self.buffers()) if t.is_cuda}
+        for d in devices or {None}:
+            settle_build(d)
 
     def drop_slot(self, slot):
         """Drop one slot's plans (a slot that keeps a narrower weight key of its own and found it stale)."""

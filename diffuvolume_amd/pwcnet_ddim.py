@@ -33,6 +33,7 @@ from torch import nn
 from . import _lib, ddim, train2d, train3d, train_net2d
 from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
 from .head import DynamicHead
+from .plans import settle_build
 from .train_tail import regress_head
 from .train_refine import warp_corr_train
 from .train_norm import bn_act
@@ -464,7 +465,9 @@ class _RefinePlan:
         """Layer i with `dil` of its dilation left to the kernel (the rest is in the tensor's de-interleave level)."""
         if (i, dil) not in self._cache:
             mod = self.mods[i]
-            self._cache[(i, dil)] = (_plan_cb2(mod, ACT_MISH, dil) if isinstance(mod, nn.Sequential) else _Block2dPlan(mod, dil))
+            plan = _plan_cb2(mod, ACT_MISH, dil) if isinstance(mod, nn.Sequential) else _Block2dPlan(mod, dil)
+            settle_build(self.conv8.wpacked.device)    # built on first use, after PlanCache.plans() returned: same guarantee
+            self._cache[(i, dil)] = plan
         return self._cache[(i, dil)]
 
     PAD_LIMIT = 1.15

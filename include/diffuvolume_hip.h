@@ -9,7 +9,10 @@
  *  - every pointer is a DEVICE pointer to a dense, contiguous row-major tensor in
  *    the reference's own layout (NCHW / NCDHW); outputs are caller-allocated;
  *  - nothing here allocates, frees, synchronises or keeps global mutable state;
- *    calls are re-entrant and are enqueued on `stream` of the current device;
+ *    calls are re-entrant and are enqueued on `stream` of the current device.  The one exception to "no global
+ *    state" are the test hooks dv_conv3d_set_s2_tile, dv_conv3d_set_c1z, dv_deconv3d_set_impl and
+ *    dv_deconv3d_pl_set_max_blocks: process-wide atomics meant for tests, not to be toggled while another thread launches;
+ *  - stream contract: every launch and memset of an entry goes to `stream`, and no entry blocks the host;
  *  - alignment: a tensor operand needs only the alignment of its element type (4 bytes for float, 8 for double) unless
  *    the entry says otherwise below.  16-byte aligned operands on rows of whole quads (W or H*W a multiple of 4) select
  *    the vector loads / stores; any other placement takes the element-wise bodies and gives the same values to within

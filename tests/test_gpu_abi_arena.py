@@ -186,8 +186,9 @@ def _sync_or_stop(what):
         pytest.exit(f"GPU fault in {what}: {e}", returncode=3)
 
 
-def run_variant(row, case, label, off, want):
-    lib = _lib.load() if DEV != "cpu" else None
+def place_operands(row, case, label, off):
+    """name -> Arena of every operand of ``case``, each displaced by ``off`` floats (tests/test_gpu_stream_contract.py places
+    its operands through this too)."""
     ar = {}
     for n, t in case.inputs.items():
         ar[n] = A.place(t, off.get(n, 0), "in", DEV, name=f"{row.name}[{label}].{n}")
@@ -195,6 +196,12 @@ def run_variant(row, case, label, off, want):
         ar[n] = A.place(t, off.get(n, 0), "out", DEV, name=f"{row.name}[{label}].{n}")
     for n, t in case.inout.items():
         ar[n] = A.place(t, off.get(n, 0), "inout", DEV, name=f"{row.name}[{label}].{n}")
+    return ar
+
+
+def run_variant(row, case, label, off, want):
+    lib = _lib.load() if DEV != "cpu" else None
+    ar = place_operands(row, case, label, off)
     p = lambda n: ar[n].data_ptr() if n in ar else None
     if case.before:
         case.before(lib)
