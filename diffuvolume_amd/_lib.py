@@ -1,5 +1,5 @@
-"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h, include/diffuvolume_hip_train.h and
-include/diffuvolume_hip_volume_train.h).
+"""ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h, include/diffuvolume_hip_train.h,
+include/diffuvolume_hip_volume_train.h and include/diffuvolume_hip_amp3d.h).
 
 There is deliberately no CPU / eager fallback: if the library is missing or a
 kernel reports an error the call raises.  ``import torch`` happens first so the
@@ -224,6 +224,18 @@ VOLUME_TRAIN_SIGNATURES = {
 }
 
 
+# Fourth table: include/diffuvolume_hip_amp3d.h, the fp16-MFMA products of the 3x3x3 stride-1 convolutions at train
+# precision "f16" (train3d.py).  Same shape as the third table; tests/test_amp3d_host.py reads it.  There is no pack entry
+# and no tuning hook here: the kernels read the module's raw float32 weight.
+AMP3D_SIGNATURES = {
+    "dv_conv3d_k3s1_f16_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, P],
+                               held_by("test_gpu_amp3d_abi.py::test_conv3d_f16_abi_offset_views_bounds_and_refusals")),
+    "dv_conv3d_wgrad_f16_workspace_floats": (c_size_t, [I, I, I, I, I, I], SIZE_ONLY),
+    "dv_conv3d_wgrad_f16_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, P],
+                                held_by("test_gpu_amp3d_abi.py::test_conv3d_wgrad_f16_abi_offset_views_bounds_and_refusals")),
+}
+
+
 class DiffuVolumeError(RuntimeError):
     pass
 
@@ -242,7 +254,8 @@ def load() -> ctypes.CDLL:
             f"{_LIB_PATH} is missing: build it with `python -m diffuvolume_amd._build` "
             "(there is no CPU fallback for the DiffuVolume hot path)")
     lib = ctypes.CDLL(os.fspath(_LIB_PATH), mode=ctypes.RTLD_GLOBAL)
-    tables = {**SIGNATURES, **TRAIN_SIGNATURES, **{k: v[:2] for k, v in VOLUME_TRAIN_SIGNATURES.items()}}
+    tables = {**SIGNATURES, **TRAIN_SIGNATURES, **{k: v[:2] for k, v in VOLUME_TRAIN_SIGNATURES.items()},
+              **{k: v[:2] for k, v in AMP3D_SIGNATURES.items()}}
     for name, (res, args) in tables.items():
         fn = getattr(lib, name)          # AttributeError => ABI mismatch, also loud
         fn.restype = res

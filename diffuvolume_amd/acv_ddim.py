@@ -350,7 +350,7 @@ class _HipPlanMixin(PlanCache, nn.Module):
             return _Plans(self)
 
 
-class ACVNet_DDIM(_HipPlanMixin):
+class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
     def __init__(self, maxdisp: int, attn_weights_only: bool = False, freeze_attn_weights: bool = False,
                  sampling_timesteps: int = 5, ensemble_cof: Optional[Sequence[float]] = None):
         super().__init__()
@@ -560,7 +560,13 @@ class ACVNet_DDIM(_HipPlanMixin):
 
     def train_forward(self, left, right, disp, mask_gt=None):
         """The reference's training branch (acv_ddim.py:372-399, :424-482) -> [pred_attention, pred0, pred1, pred2].
-        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order)."""
+        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order).
+        Runs at ``self.train_precision`` (``set_train_precision``): every ``train3d`` call below, the no-grad statistics
+        pass and the hourglasses' helpers included, sees it for the length of this call, on this thread only."""
+        with self._train_scope():
+            return self._train_forward(left, right, disp, mask_gt)
+
+    def _train_forward(self, left, right, disp, mask_gt=None):
         if not left.is_cuda:
             raise NotImplementedError("training runs on the MI355X only (model.cuda()); no CPU path")
         fl = self.feature_extraction(left)["gwc_feature"]

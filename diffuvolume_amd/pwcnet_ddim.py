@@ -678,7 +678,7 @@ def PWCNet_GC(d):
     return PWCNet(d, use_concat_volume=True)
 
 
-class PWCNet_ddim(_PWCCommon, nn.Module):
+class PWCNet_ddim(train3d.TrainPrecision, _PWCCommon, nn.Module):
     def __init__(self, maxdisp: int, use_concat_volume: bool = True, sampling_timesteps: int = 3,
                  ensemble_cof: Optional[Sequence[float]] = None):
         super().__init__()
@@ -817,7 +817,13 @@ class PWCNet_ddim(_PWCCommon, nn.Module):
     def train_forward(self, left, right, disp):
         """The reference's training branch (pwcnet_ddim.py:604-735) -> [pred0, combine, pred1, pred2, pred3,
         disp_finetune], each [B,H,W].  ``disp``: the quarter-resolution disparity [B,1,H/4,W/4] (KITTI12/main.py:148-150).
-        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order)."""
+        Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order).
+        Runs at ``self.train_precision`` (``set_train_precision``): every ``train3d`` call below sees it for the length of
+        this call, on this thread only."""
+        with self._train_scope():
+            return self._train_forward(left, right, disp)
+
+    def _train_forward(self, left, right, disp):
         if not left.is_cuda:
             raise NotImplementedError("training runs on the MI355X only (model.cuda()); no CPU path")
         hh, ww = left.shape[-2], left.shape[-1]

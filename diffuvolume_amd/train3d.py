@@ -15,9 +15,20 @@ its own for both gradients (csrc/deconv3d_k4_bwd.hip); ``feature_gate_train(cv, 
 ``sigmoid(logit) * cv`` with ``dv_feature_gate_bwd_f32`` as its backward.
 BatchNorm3d and the activation behind it are ``train_norm.py``'s.  ``DV_TRAIN_CONV3D=torch`` routes every function to its torch expression (``F.conv3d``,
 ``F.conv_transpose3d``, ``torch.sigmoid(logit).unsqueeze(2) * cv``) instead (A/B runs, tests).  CPU tensors raise, as
-everywhere on the hot path."""
+everywhere on the hot path.
+
+Train precision ``"f16"`` (``conv3d(..., precision=)``; ``ACVNet_DDIM`` / ``PWCNet_ddim.set_train_precision`` set it for
+their ``train_forward`` through ``precision_scope``; default ``"f32"``, where nothing changes): the 3x3x3 stride-1
+convolutions with more than one output channel run all three products on the fp16 matrix instruction --
+``dv_conv3d_k3s1_f16_f32`` (csrc/conv3d_f16.hip: forward, and with ``transpose_flip`` the input gradient, on the raw
+weight, no packed copy) and ``dv_conv3d_wgrad_f16_f32`` (csrc/conv3d_wgrad_f16.hip), include/diffuvolume_hip_amp3d.h:
+float32 tensors, operands rounded to fp16 while staged, fp32 sums, no result rounded.  Every other layer class keeps its
+float32 kernels.  Under ``DV_TRAIN_CONV3D=torch`` those layers run ``F.conv3d`` under a real fp16 ``torch.autocast``
+and return float32 (the reference route of the tests)."""
 from __future__ import annotations
 
+import contextlib
+import contextvars
 import functools
 from typing import Optional
 
@@ -29,6 +40,96 @@ from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan, feature_gate
 
 
 route = functools.partial(_env.route, "DV_TRAIN_CONV3D")
+
+PRECISIONS = ("f32", "f16")
+# The train precision of the model call in progress: ``ACVNet_DDIM.train_forward`` / ``PWCNet_ddim.train_forward`` set it
+# for their own call (``precision_scope``), ``conv3d(..., precision=None)`` reads it.  A ContextVar: every thread (two
+# replicas training side by side) and every nested call has its own value, and nothing outside a model call ever sees
+# anything but "f32".  The backward never reads it -- the autograd engine runs on threads of its own -- but the precision
+# ``Conv3dFn.forward`` saved on ``ctx``.
+_ambient_precision = contextvars.ContextVar("dv_train3d_precision", default="f32")
+
+
+def check_precision(precision: str) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"train precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
+@contextlib.contextmanager
+def precision_scope(precision: str):
+    """Every ``conv3d`` / ``conv3d_module`` call of this thread inside the block that names no precision runs at
+    ``precision``."""
+    token = _ambient_precision.set(check_precision(precision))
+    try:
+        yield
+    finally:
+        _ambient_precision.reset(token)
+
+
+def ambient_precision() -> str:
+    return _ambient_precision.get()
+
+
+class TrainPrecision:
+    """What ``ACVNet_DDIM`` and ``PWCNet_ddim`` add to nn.Module for mixed-precision training (modelled on
+    ``update._Planned``): ``set_train_precision("f32" | "f16")``, the ``train_precision`` property, and
+    ``_train_scope()``, which their ``train_forward`` runs under.  Eval and ``no_grad`` inference never look at it."""
+
+    _train_precision = "f32"
+
+    def set_train_precision(self, precision: str):
+        """"f32" (default) or "f16": the 3x3x3 stride-1 convolutions of the model's 3-D stack with more than one output
+        channel run their three products on the fp16 matrix instruction (operands rounded to fp16, fp32 sums, float32
+        results); every other layer keeps its float32 kernels."""
+        self._train_precision = check_precision(precision)
+        return self
+
+    @property
+    def train_precision(self) -> str:
+        return self._train_precision
+
+    def _train_scope(self):
+        return precision_scope(self._train_precision)
+
+
+def takes_f16(k: int, stride: int, cout: int) -> bool:
+    """The layer class that "f16" moves to the fp16 matrix instruction; every other one keeps its float32 kernels."""
+    return k == 3 and stride == 1 and cout > 1
+
+
+def conv3d_k3s1_f16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    transpose_flip: bool = False) -> torch.Tensor:
+    """conv(r16(x), r16(w)) + bias of a 3x3x3 stride-1 convolution, unrounded float32 (csrc/conv3d_f16.hip).  ``w`` is the
+    raw weight [Cout,Cin,3,3,3]; with ``transpose_flip`` it is [Cin,Cout,3,3,3] and read as w.flip(2,3,4).transpose(0,1)
+    (the input gradient, ``x`` being the output gradient)."""
+    x, w = x.contiguous(), w.contiguous()
+    b, cin, d, h, wd = x.shape
+    cout = w.shape[1] if transpose_flip else w.shape[0]
+    if tuple(w.shape) != ((cin, cout, 3, 3, 3) if transpose_flip else (cout, cin, 3, 3, 3)):
+        raise _lib.DiffuVolumeError(f"conv3d f16: weight {tuple(w.shape)} against input {tuple(x.shape)}")
+    y = torch.empty((b, cout, d, h, wd), dtype=torch.float32, device=x.device)
+    _lib.launch("dv_conv3d_k3s1_f16_f32", x.device, x.data_ptr(), w.data_ptr(),
+                _lib.ptr(None if bias is None else bias.contiguous()), y.data_ptr(), b, cin, d, h, wd, cout, 3,
+                int(transpose_flip))
+    return y
+
+
+def conv3d_weight_grad_f16(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """dW [Cout,Cin,3,3,3] = sum r16(g) r16(x) of a 3x3x3 stride-1 convolution, unrounded float32
+    (csrc/conv3d_wgrad_f16.hip)."""
+    x, g = x.contiguous(), g.contiguous()
+    b, cin, d, h, w = x.shape
+    cout = g.shape[1]
+    if tuple(g.shape) != (b, cout, d, h, w):
+        raise _lib.DiffuVolumeError(f"conv3d f16 weight gradient: input {tuple(x.shape)} against gradient {tuple(g.shape)}")
+    ws = _lib.workspace("dv_conv3d_wgrad_f16_workspace_floats", x.device, b, cin, d, h, w, cout)
+    if ws is None:
+        raise _lib.DiffuVolumeError(f"dv_conv3d_wgrad_f16_f32 does not take the shape {tuple(x.shape)} -> {cout} channels")
+    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    _lib.launch("dv_conv3d_wgrad_f16_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d, h,
+                w, cout)
+    return dw
 
 
 def conv3d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int, cout: int) -> torch.Tensor:
@@ -50,15 +151,19 @@ def _plan(w: torch.Tensor, stride: int, bias: Optional[torch.Tensor] = None) -> 
 
 class Conv3dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, stride):
+    def forward(ctx, x, weight, bias, stride, precision="f32"):
         _lib.check_f32(x, "x")
         _lib.check_f32(weight, "weight")
+        check_precision(precision)
         k = weight.shape[2]
         if tuple(weight.shape[2:]) != (k, k, k) or k not in (1, 3) or stride not in (1, 2) or (k == 1 and stride != 1):
             raise _lib.DiffuVolumeError(f"unsupported Conv3d: kernel {tuple(weight.shape[2:])}, stride {stride}")
         x = x.contiguous()
         ctx.save_for_backward(x, weight)
         ctx.stride, ctx.has_bias = stride, bias is not None
+        ctx.f16 = precision == "f16" and takes_f16(k, stride, weight.shape[0])
+        if ctx.f16:
+            return conv3d_k3s1_f16(x.detach(), weight.detach(), None if bias is None else bias.detach())
         return _plan(weight.detach(), stride, None if bias is None else bias.detach())(x)
 
     @staticmethod
@@ -68,7 +173,11 @@ class Conv3dFn(torch.autograd.Function):
         g = g.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if k == 1:
+            # the precision saved by forward, never an ambient value.  A layer with ONE input channel has a one-channel
+            # input gradient, which the fp16 entry refuses as it does the 32 -> 1 heads: float32 kernel, as at "f32"
+            if ctx.f16 and w.shape[1] > 1:
+                dx = conv3d_k3s1_f16(g, w.detach(), None, transpose_flip=True)
+            elif k == 1:
                 dx = _plan(w.detach().transpose(0, 1), 1)(g)
             elif stride == 1:
                 dx = _plan(w.detach().flip(2, 3, 4).transpose(0, 1), 1)(g)
@@ -77,10 +186,10 @@ class Conv3dFn(torch.autograd.Function):
                     raise _lib.DiffuVolumeError(f"stride-2 input gradient needs even dims, got {tuple(x.shape[2:])}")
                 dx = Deconv3dPlan(w.detach().contiguous(), None, act=ACT_NONE)(g)
         if ctx.needs_input_grad[1]:
-            dw = conv3d_weight_grad(x, g, k, stride, w.shape[0])
+            dw = conv3d_weight_grad_f16(x, g) if ctx.f16 else conv3d_weight_grad(x, g, k, stride, w.shape[0])
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = g.sum(dim=(0, 2, 3, 4))
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 class ConvTranspose3dFn(torch.autograd.Function):
@@ -196,11 +305,20 @@ class FeatureGateFn(torch.autograd.Function):
         return (dcv if ctx.needs_input_grad[0] else None), (dlogit if ctx.needs_input_grad[1] else None)
 
 
-def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1) -> torch.Tensor:
+def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1,
+           precision: Optional[str] = None) -> torch.Tensor:
+    """``precision``: "f32" | "f16"; None = the precision of the model call in progress (``precision_scope``), "f32"
+    outside one.  "f16" moves the 3x3x3 stride-1 layers with more than one output channel to the fp16 kernels."""
     k = weight.shape[2]
+    precision = check_precision(ambient_precision() if precision is None else precision)
     if route() == "torch":
+        if precision == "f16" and takes_f16(k, stride, weight.shape[0]) and x.is_cuda:
+            # the A/B and reference route of "f16": what a reference user gets from autocast (operands AND result in fp16)
+            with torch.autocast("cuda", dtype=torch.float16):
+                y = F.conv3d(x, weight, bias, stride=stride, padding=1)
+            return y.float()
         return F.conv3d(x, weight, bias, stride=stride, padding=(k - 1) // 2)
-    return Conv3dFn.apply(x, weight, bias, stride)
+    return Conv3dFn.apply(x, weight, bias, stride, precision)
 
 
 def conv_transpose3d(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -221,9 +339,9 @@ def feature_gate_train(cv: torch.Tensor, logit: torch.Tensor) -> torch.Tensor:
     return FeatureGateFn.apply(cv, logit)
 
 
-def conv3d_module(m: torch.nn.Conv3d, x: torch.Tensor) -> torch.Tensor:
+def conv3d_module(m: torch.nn.Conv3d, x: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
     """An nn.Conv3d of the aggregation stack (cubic kernel, padding (k-1)/2) on the differentiable HIP route."""
-    return conv3d(x, m.weight, m.bias, stride=m.stride[0])
+    return conv3d(x, m.weight, m.bias, stride=m.stride[0], precision=precision)
 
 
 def conv_transpose3d_module(m: torch.nn.ConvTranspose3d, x: torch.Tensor) -> torch.Tensor:
