@@ -16,14 +16,16 @@ from .train_patch import patch_volume_train
 from .train_attn import window_attention_train
 from .train_net2d import resize_bilinear_train
 from .train_loss import masked_loss_train, sequence_loss_train
-from .train3d import conv3d as conv3d_train, conv3d_k3s1_f16, conv3d_weight_grad_f16, precision_scope as train_precision_scope
+from .train3d import (conv3d as conv3d_train, conv3d_k3s1_bf16, conv3d_k3s1_f16, conv3d_weight_grad_bf16,
+                      conv3d_weight_grad_f16, precision_scope as train_precision_scope)
 
 __all__ = ["ACVNet", "ACVNet_DDIM", "PWCNet", "PWCNet_ddim", "__models__", "build_gwc_volume", "build_concat_volume",
            "build_concat_attention_volume", "AttentionConcatVolume", "disparity_regression", "upsample_softmax_regress",
            "upsample_softmax_regress_train", "build_gwc_volume_train", "build_concat_volume_train",
            "warp_corr_train", "batch_norm_act_train", "patch_volume_train", "window_attention_train",
            "resize_bilinear_train", "masked_loss_train", "sequence_loss_train",
-           "conv3d_train", "conv3d_k3s1_f16", "conv3d_weight_grad_f16", "train_precision_scope",
+           "conv3d_train", "conv3d_k3s1_f16", "conv3d_weight_grad_f16", "conv3d_k3s1_bf16", "conv3d_weight_grad_bf16",
+           "train_precision_scope",
            "DiffuVolumeError", "lib_path", "load", "model_loss_train", "model_loss_train_freeze_attn",
            "model_loss_train_attn_only", "model_loss_test", "model_loss_kitti12"]
 # KITTI12/models/__init__.py:5-9: the origin network under both registry names and the DiffuVolume flavour

@@ -236,6 +236,17 @@ AMP3D_SIGNATURES = {
 }
 
 
+# Fifth table: include/diffuvolume_hip_amp3d_bf16.h, the bf16-MFMA twins of the fourth table (train precision "bf16"):
+# the same signatures, the same kernels instantiated for the other element type.  tests/test_amp3d_bf16_host.py reads it.
+AMP3D_BF16_SIGNATURES = {
+    "dv_conv3d_k3s1_bf16_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, P],
+                                held_by("test_gpu_amp3d_bf16_abi.py::test_conv3d_bf16_abi_offset_views_bounds_and_refusals")),
+    "dv_conv3d_wgrad_bf16_workspace_floats": (c_size_t, [I, I, I, I, I, I], SIZE_ONLY),
+    "dv_conv3d_wgrad_bf16_f32": (c_int, [P, P, P, P, I, I, I, I, I, I, P],
+                                 held_by("test_gpu_amp3d_bf16_abi.py::test_conv3d_wgrad_bf16_abi_offset_views_bounds_and_refusals")),
+}
+
+
 class DiffuVolumeError(RuntimeError):
     pass
 
@@ -255,7 +266,7 @@ def load() -> ctypes.CDLL:
             "(there is no CPU fallback for the DiffuVolume hot path)")
     lib = ctypes.CDLL(os.fspath(_LIB_PATH), mode=ctypes.RTLD_GLOBAL)
     tables = {**SIGNATURES, **TRAIN_SIGNATURES, **{k: v[:2] for k, v in VOLUME_TRAIN_SIGNATURES.items()},
-              **{k: v[:2] for k, v in AMP3D_SIGNATURES.items()}}
+              **{k: v[:2] for k, v in AMP3D_SIGNATURES.items()}, **{k: v[:2] for k, v in AMP3D_BF16_SIGNATURES.items()}}
     for name, (res, args) in tables.items():
         fn = getattr(lib, name)          # AttributeError => ABI mismatch, also loud
         fn.restype = res

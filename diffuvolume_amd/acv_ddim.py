@@ -561,7 +561,8 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
     def train_forward(self, left, right, disp, mask_gt=None):
         """The reference's training branch (acv_ddim.py:372-399, :424-482) -> [pred_attention, pred0, pred1, pred2].
         Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order).
-        Runs at ``self.train_precision`` (``set_train_precision``): every ``train3d`` call below, the no-grad statistics
+        Runs at ``self.train_precision`` ("f32", "f16" or "bf16"; ``set_train_precision``, which takes ``torch.bfloat16``
+        for the last): every ``train3d`` call below, the no-grad statistics
         pass and the hourglasses' helpers included, sees it for the length of this call, on this thread only."""
         with self._train_scope():
             return self._train_forward(left, right, disp, mask_gt)

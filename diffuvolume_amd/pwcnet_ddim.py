@@ -818,8 +818,8 @@ class PWCNet_ddim(train3d.TrainPrecision, _PWCCommon, nn.Module):
         """The reference's training branch (pwcnet_ddim.py:604-735) -> [pred0, combine, pred1, pred2, pred3,
         disp_finetune], each [B,H,W].  ``disp``: the quarter-resolution disparity [B,1,H/4,W/4] (KITTI12/main.py:148-150).
         Draws ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order).
-        Runs at ``self.train_precision`` (``set_train_precision``): every ``train3d`` call below sees it for the length of
-        this call, on this thread only."""
+        Runs at ``self.train_precision`` ("f32", "f16" or "bf16"; ``set_train_precision``, which takes ``torch.bfloat16``
+        for the last): every ``train3d`` call below sees it for the length of this call, on this thread only."""
         with self._train_scope():
             return self._train_forward(left, right, disp)
 

@@ -24,7 +24,14 @@ convolutions with more than one output channel run all three products on the fp1
 weight, no packed copy) and ``dv_conv3d_wgrad_f16_f32`` (csrc/conv3d_wgrad_f16.hip), include/diffuvolume_hip_amp3d.h:
 float32 tensors, operands rounded to fp16 while staged, fp32 sums, no result rounded.  Every other layer class keeps its
 float32 kernels.  Under ``DV_TRAIN_CONV3D=torch`` those layers run ``F.conv3d`` under a real fp16 ``torch.autocast``
-and return float32 (the reference route of the tests)."""
+and return float32 (the reference route of the tests).
+
+Train precision ``"bf16"`` (``set_train_precision(torch.bfloat16)``) is the same route on the bf16 matrix instruction:
+``dv_conv3d_k3s1_bf16_f32`` (csrc/conv3d_bf16.hip) and ``dv_conv3d_wgrad_bf16_f32`` (csrc/conv3d_wgrad_bf16.hip),
+include/diffuvolume_hip_amp3d_bf16.h -- the kernels of ``"f16"`` (csrc/conv3d_mp.h, csrc/conv3d_wgrad_mp.h) instantiated
+for the other element type: operands rounded to bfloat16 while staged, fp32 sums, no result rounded.  bfloat16 has
+float32's exponent range, so there is no loss scaling and no skipped step.  Under ``DV_TRAIN_CONV3D=torch`` the layers run
+``F.conv3d`` under a real bf16 ``torch.autocast`` and return float32."""
 from __future__ import annotations
 
 import contextlib
@@ -41,7 +48,12 @@ from .submodule import ACT_NONE, Conv3dPlan, Deconv3dPlan, feature_gate
 
 route = functools.partial(_env.route, "DV_TRAIN_CONV3D")
 
-PRECISIONS = ("f32", "f16")
+PRECISIONS = ("f32", "f16", "bf16")
+# the reduced precisions (each also the infix of its ABI table's entries) -> the dtype torch.autocast names it by
+REDUCED = {"f16": torch.float16, "bf16": torch.bfloat16}
+# what ``TrainPrecision.set_train_precision`` takes: the two names it has always taken, and the dtypes as torch.autocast
+# names them.  "bf16" has no string spelling on the model method: the dtype is its documented one.
+_MODEL_PRECISIONS = {"f32": "f32", "f16": "f16", torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
 # The train precision of the model call in progress: ``ACVNet_DDIM.train_forward`` / ``PWCNet_ddim.train_forward`` set it
 # for their own call (``precision_scope``), ``conv3d(..., precision=None)`` reads it.  A ContextVar: every thread (two
 # replicas training side by side) and every nested call has its own value, and nothing outside a model call ever sees
@@ -73,16 +85,26 @@ def ambient_precision() -> str:
 
 class TrainPrecision:
     """What ``ACVNet_DDIM`` and ``PWCNet_ddim`` add to nn.Module for mixed-precision training (modelled on
-    ``update._Planned``): ``set_train_precision("f32" | "f16")``, the ``train_precision`` property, and
+    ``update._Planned``): ``set_train_precision("f32" | "f16" | torch.float32 | torch.float16 | torch.bfloat16)``, the
+    ``train_precision`` property (``"f32"``, ``"f16"`` or ``"bf16"``), and
     ``_train_scope()``, which their ``train_forward`` runs under.  Eval and ``no_grad`` inference never look at it."""
 
     _train_precision = "f32"
 
-    def set_train_precision(self, precision: str):
+    def set_train_precision(self, precision):
         """"f32" (default) or "f16": the 3x3x3 stride-1 convolutions of the model's 3-D stack with more than one output
         channel run their three products on the fp16 matrix instruction (operands rounded to fp16, fp32 sums, float32
-        results); every other layer keeps its float32 kernels."""
-        self._train_precision = check_precision(precision)
+        results); every other layer keeps its float32 kernels.
+
+        Also ``torch.float32``, ``torch.float16`` and ``torch.bfloat16``, named as ``torch.autocast`` names them;
+        ``train_precision`` then reads "f32", "f16" or "bf16".  ``torch.bfloat16`` is THE spelling of bf16 here: the same
+        layers on the bf16 matrix instruction (operands rounded to bfloat16), no ``GradScaler`` needed.  The bare string
+        "bf16" raises ValueError on this method, as do "fp16", "", None, 16 and any other dtype
+        (``train3d.precision_scope("bf16")`` and ``conv3d(..., precision="bf16")`` take the name)."""
+        if isinstance(precision, bool) or not isinstance(precision, (str, torch.dtype)) or precision not in _MODEL_PRECISIONS:
+            raise ValueError('train precision must be "f32", "f16", torch.float32, torch.float16 or torch.bfloat16, '
+                             f"got {precision!r}")
+        self._train_precision = _MODEL_PRECISIONS[precision]
         return self
 
     @property
@@ -94,8 +116,39 @@ class TrainPrecision:
 
 
 def takes_f16(k: int, stride: int, cout: int) -> bool:
-    """The layer class that "f16" moves to the fp16 matrix instruction; every other one keeps its float32 kernels."""
+    """The layer class that "f16" / "bf16" move to the fp16 / bf16 matrix instruction; every other one keeps its float32
+    kernels."""
     return k == 3 and stride == 1 and cout > 1
+
+
+def _conv3d_k3s1_mp(elem: str, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], transpose_flip: bool):
+    """``dv_conv3d_k3s1_<elem>_f32``, ``elem`` in ("f16", "bf16")."""
+    x, w = x.contiguous(), w.contiguous()
+    b, cin, d, h, wd = x.shape
+    cout = w.shape[1] if transpose_flip else w.shape[0]
+    if tuple(w.shape) != ((cin, cout, 3, 3, 3) if transpose_flip else (cout, cin, 3, 3, 3)):
+        raise _lib.DiffuVolumeError(f"conv3d {elem}: weight {tuple(w.shape)} against input {tuple(x.shape)}")
+    y = torch.empty((b, cout, d, h, wd), dtype=torch.float32, device=x.device)
+    _lib.launch(f"dv_conv3d_k3s1_{elem}_f32", x.device, x.data_ptr(), w.data_ptr(),
+                _lib.ptr(None if bias is None else bias.contiguous()), y.data_ptr(), b, cin, d, h, wd, cout, 3,
+                int(transpose_flip))
+    return y
+
+
+def _conv3d_weight_grad_mp(elem: str, x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """``dv_conv3d_wgrad_<elem>_f32``, ``elem`` in ("f16", "bf16")."""
+    x, g = x.contiguous(), g.contiguous()
+    b, cin, d, h, w = x.shape
+    cout = g.shape[1]
+    if tuple(g.shape) != (b, cout, d, h, w):
+        raise _lib.DiffuVolumeError(f"conv3d {elem} weight gradient: input {tuple(x.shape)} against gradient {tuple(g.shape)}")
+    ws = _lib.workspace(f"dv_conv3d_wgrad_{elem}_workspace_floats", x.device, b, cin, d, h, w, cout)
+    if ws is None:
+        raise _lib.DiffuVolumeError(f"dv_conv3d_wgrad_{elem}_f32 does not take the shape {tuple(x.shape)} -> {cout} channels")
+    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    _lib.launch(f"dv_conv3d_wgrad_{elem}_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d,
+                h, w, cout)
+    return dw
 
 
 def conv3d_k3s1_f16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -103,33 +156,24 @@ def conv3d_k3s1_f16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tenso
     """conv(r16(x), r16(w)) + bias of a 3x3x3 stride-1 convolution, unrounded float32 (csrc/conv3d_f16.hip).  ``w`` is the
     raw weight [Cout,Cin,3,3,3]; with ``transpose_flip`` it is [Cin,Cout,3,3,3] and read as w.flip(2,3,4).transpose(0,1)
     (the input gradient, ``x`` being the output gradient)."""
-    x, w = x.contiguous(), w.contiguous()
-    b, cin, d, h, wd = x.shape
-    cout = w.shape[1] if transpose_flip else w.shape[0]
-    if tuple(w.shape) != ((cin, cout, 3, 3, 3) if transpose_flip else (cout, cin, 3, 3, 3)):
-        raise _lib.DiffuVolumeError(f"conv3d f16: weight {tuple(w.shape)} against input {tuple(x.shape)}")
-    y = torch.empty((b, cout, d, h, wd), dtype=torch.float32, device=x.device)
-    _lib.launch("dv_conv3d_k3s1_f16_f32", x.device, x.data_ptr(), w.data_ptr(),
-                _lib.ptr(None if bias is None else bias.contiguous()), y.data_ptr(), b, cin, d, h, wd, cout, 3,
-                int(transpose_flip))
-    return y
+    return _conv3d_k3s1_mp("f16", x, w, bias, transpose_flip)
+
+
+def conv3d_k3s1_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                     transpose_flip: bool = False) -> torch.Tensor:
+    """``conv3d_k3s1_f16`` with both operands rounded to bfloat16 instead (csrc/conv3d_bf16.hip)."""
+    return _conv3d_k3s1_mp("bf16", x, w, bias, transpose_flip)
 
 
 def conv3d_weight_grad_f16(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """dW [Cout,Cin,3,3,3] = sum r16(g) r16(x) of a 3x3x3 stride-1 convolution, unrounded float32
     (csrc/conv3d_wgrad_f16.hip)."""
-    x, g = x.contiguous(), g.contiguous()
-    b, cin, d, h, w = x.shape
-    cout = g.shape[1]
-    if tuple(g.shape) != (b, cout, d, h, w):
-        raise _lib.DiffuVolumeError(f"conv3d f16 weight gradient: input {tuple(x.shape)} against gradient {tuple(g.shape)}")
-    ws = _lib.workspace("dv_conv3d_wgrad_f16_workspace_floats", x.device, b, cin, d, h, w, cout)
-    if ws is None:
-        raise _lib.DiffuVolumeError(f"dv_conv3d_wgrad_f16_f32 does not take the shape {tuple(x.shape)} -> {cout} channels")
-    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    _lib.launch("dv_conv3d_wgrad_f16_f32", x.device, x.data_ptr(), g.data_ptr(), dw.data_ptr(), ws.data_ptr(), b, cin, d, h,
-                w, cout)
-    return dw
+    return _conv3d_weight_grad_mp("f16", x, g)
+
+
+def conv3d_weight_grad_bf16(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """``conv3d_weight_grad_f16`` with both operands rounded to bfloat16 instead (csrc/conv3d_wgrad_bf16.hip)."""
+    return _conv3d_weight_grad_mp("bf16", x, g)
 
 
 def conv3d_weight_grad(x: torch.Tensor, g: torch.Tensor, k: int, stride: int, cout: int) -> torch.Tensor:
@@ -161,9 +205,10 @@ class Conv3dFn(torch.autograd.Function):
         x = x.contiguous()
         ctx.save_for_backward(x, weight)
         ctx.stride, ctx.has_bias = stride, bias is not None
-        ctx.f16 = precision == "f16" and takes_f16(k, stride, weight.shape[0])
-        if ctx.f16:
-            return conv3d_k3s1_f16(x.detach(), weight.detach(), None if bias is None else bias.detach())
+        # the element type of this layer's three products: "f16" | "bf16", or None for the float32 kernels
+        ctx.elem = precision if precision in REDUCED and takes_f16(k, stride, weight.shape[0]) else None
+        if ctx.elem:
+            return _conv3d_k3s1_mp(ctx.elem, x.detach(), weight.detach(), None if bias is None else bias.detach(), False)
         return _plan(weight.detach(), stride, None if bias is None else bias.detach())(x)
 
     @staticmethod
@@ -174,9 +219,9 @@ class Conv3dFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             # the precision saved by forward, never an ambient value.  A layer with ONE input channel has a one-channel
-            # input gradient, which the fp16 entry refuses as it does the 32 -> 1 heads: float32 kernel, as at "f32"
-            if ctx.f16 and w.shape[1] > 1:
-                dx = conv3d_k3s1_f16(g, w.detach(), None, transpose_flip=True)
+            # input gradient, which the fp16 and bf16 entries refuse as they do the 32 -> 1 heads: float32 kernel, as at "f32"
+            if ctx.elem and w.shape[1] > 1:
+                dx = _conv3d_k3s1_mp(ctx.elem, g, w.detach(), None, True)
             elif k == 1:
                 dx = _plan(w.detach().transpose(0, 1), 1)(g)
             elif stride == 1:
@@ -186,7 +231,7 @@ class Conv3dFn(torch.autograd.Function):
                     raise _lib.DiffuVolumeError(f"stride-2 input gradient needs even dims, got {tuple(x.shape[2:])}")
                 dx = Deconv3dPlan(w.detach().contiguous(), None, act=ACT_NONE)(g)
         if ctx.needs_input_grad[1]:
-            dw = conv3d_weight_grad_f16(x, g) if ctx.f16 else conv3d_weight_grad(x, g, k, stride, w.shape[0])
+            dw = _conv3d_weight_grad_mp(ctx.elem, x, g) if ctx.elem else conv3d_weight_grad(x, g, k, stride, w.shape[0])
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = g.sum(dim=(0, 2, 3, 4))
         return dx, dw, db, None, None
@@ -307,14 +352,16 @@ class FeatureGateFn(torch.autograd.Function):
 
 def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1,
            precision: Optional[str] = None) -> torch.Tensor:
-    """``precision``: "f32" | "f16"; None = the precision of the model call in progress (``precision_scope``), "f32"
-    outside one.  "f16" moves the 3x3x3 stride-1 layers with more than one output channel to the fp16 kernels."""
+    """``precision``: "f32" | "f16" | "bf16"; None = the precision of the model call in progress (``precision_scope``),
+    "f32" outside one.  "f16" / "bf16" move the 3x3x3 stride-1 layers with more than one output channel to the fp16 / bf16
+    kernels."""
     k = weight.shape[2]
     precision = check_precision(ambient_precision() if precision is None else precision)
     if route() == "torch":
-        if precision == "f16" and takes_f16(k, stride, weight.shape[0]) and x.is_cuda:
-            # the A/B and reference route of "f16": what a reference user gets from autocast (operands AND result in fp16)
-            with torch.autocast("cuda", dtype=torch.float16):
+        if precision in REDUCED and takes_f16(k, stride, weight.shape[0]) and x.is_cuda:
+            # the A/B and reference route of "f16" / "bf16": what a reference user gets from autocast (operands AND result
+            # in the 16-bit type)
+            with torch.autocast("cuda", dtype=REDUCED[precision]):
                 y = F.conv3d(x, weight, bias, stride=stride, padding=1)
             return y.float()
         return F.conv3d(x, weight, bias, stride=stride, padding=(k - 1) // 2)

@@ -1,15 +1,17 @@
 """Time the ACVNet_DDIM and PWCNet_ddim training steps (forward, loss, backward, Adam) at the reference's training shape --
 B = 4 pairs of 256 x 512, the setup of tools/bench_train_step.py and tools/bench_pcw_train_step.py -- at train precision
-"f32" and "f16" (``set_train_precision``), alternating the two in one process, and time the three products of the
-3x3x3 stride-1 layers alone (forward, input gradient, weight gradient) on their fp16 kernels (csrc/conv3d_f16.hip,
-csrc/conv3d_wgrad_f16.hip), on the float32 kernels they replace and on MIOpen fp16 (torch, half tensors).
+"f32", "f16" and "bf16" (``set_train_precision``), alternating the three in one process, and time the three products of
+the 3x3x3 stride-1 layers alone (forward, input gradient, weight gradient) on their fp16 kernels (csrc/conv3d_f16.hip,
+csrc/conv3d_wgrad_f16.hip), on their bf16 twins (csrc/conv3d_bf16.hip, csrc/conv3d_wgrad_bf16.hip), on the float32
+kernels they replace and on MIOpen fp16 (torch, half tensors).
 
-Per product: median and min-max of the runs, the fraction of the fp16 MFMA peak (16 x 157.3 TFLOP/s) and of 8 TB/s on the
+Per product: median and min-max of the runs, the fraction of the 16-bit MFMA peak (16 x 157.3 TFLOP/s) and of 8 TB/s on the
 COUNTED bytes -- every operand read once and every result written once as float32 (the weight gradient: its partials
 written and read once more), which is what the kernels cannot avoid, not what they move.  Peak memory per step is
-torch.cuda.max_memory_allocated around the timed runs.  Writes profiles/train_step_amp_bench.json (or --out).
+torch.cuda.max_memory_allocated around the timed runs.  Writes profiles/train_step_amp_bf16_bench.json (or --out);
+profiles/train_step_amp_bench.json is the record of the two-arm tool before "bf16" and is left as it is.
 
-    python tools/bench_train_step_amp.py [--runs 5] [--skip-steps] [--out profiles/train_step_amp_bench.json]"""
+    python tools/bench_train_step_amp.py [--runs 5] [--skip-steps] [--out profiles/train_step_amp_bf16_bench.json]"""
 import argparse
 import json
 import os
@@ -69,13 +71,16 @@ def products(batch, reps):
         plan32t = train3d._plan(w.flip(2, 3, 4).transpose(0, 1), 1)
         arms = {
             "forward": (4.0 * vox * (cin + cout) + wbytes,
-                        {"f16": lambda: train3d.conv3d_k3s1_f16(x, w), "f32": lambda: plan32(x),
+                        {"f16": lambda: train3d.conv3d_k3s1_f16(x, w), "bf16": lambda: train3d.conv3d_k3s1_bf16(x, w),
+                         "f32": lambda: plan32(x),
                          "miopen_f16": lambda: F.conv3d(xh, wh, padding=1)}),
             "input_gradient": (4.0 * vox * (cin + cout) + wbytes,
-                               {"f16": lambda: train3d.conv3d_k3s1_f16(g, w, transpose_flip=True), "f32": lambda: plan32t(g),
+                               {"f16": lambda: train3d.conv3d_k3s1_f16(g, w, transpose_flip=True),
+                                "bf16": lambda: train3d.conv3d_k3s1_bf16(g, w, transpose_flip=True), "f32": lambda: plan32t(g),
                                 "miopen_f16": lambda: torch.nn.grad.conv3d_input(xh.shape, wh, gh, padding=1)}),
             "weight_gradient": (4.0 * vox * (cin + cout) + wbytes + 8.0 * ws,
                                 {"f16": lambda: train3d.conv3d_weight_grad_f16(x, g),
+                                 "bf16": lambda: train3d.conv3d_weight_grad_bf16(x, g),
                                  "f32": lambda: train3d.conv3d_weight_grad(x, g, 3, 1, cout),
                                  "miopen_f16": lambda: torch.nn.grad.conv3d_weight(xh, wh.shape, gh, padding=1)}),
         }
@@ -93,8 +98,12 @@ def products(batch, reps):
             row["f16_frac_hbm_peak"] = round(nbytes / (med * 1e-3) / PEAK_HBM, 4)
             row["f32_over_f16"] = round(row["ms"]["f32"]["median"] / med, 3)
             row["miopen_f16_over_f16"] = round(row["ms"]["miopen_f16"]["median"] / med, 3)
+            bmed = row["ms"]["bf16"]["median"]
+            row["bf16_over_f16"] = round(bmed / med, 3)
+            row["bf16_within_f16_range"] = row["ms"]["f16"]["min"] <= bmed <= row["ms"]["f16"]["max"]
             rows.append(row)
             print(f"  {name:9s} {product:16s} f16 {med:7.3f} ms ({row['ms']['f16']['min']:.3f}-{row['ms']['f16']['max']:.3f})  "
+                  f"bf16 {bmed:7.3f} ({row['ms']['bf16']['min']:.3f}-{row['ms']['bf16']['max']:.3f})  "
                   f"f32 {row['ms']['f32']['median']:7.3f}  MIOpen f16 {row['ms']['miopen_f16']['median']:7.3f}  "
                   f"{row['f16_frac_mfma_peak']:.3f} of MFMA peak, {row['f16_frac_hbm_peak']:.3f} of 8 TB/s", flush=True)
         del x, g, w, xh, gh, wh, plan32, plan32t
@@ -123,15 +132,16 @@ def model_steps(kind, batch, height, width, runs, warmup):
         opt.step()
         return float(loss.detach())
 
-    times, peak = {"f32": [], "f16": []}, {}
+    times, peak = {"f32": [], "f16": [], "bf16": []}, {}
+    dtype = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
     for p in times:
-        model.set_train_precision(p)
+        model.set_train_precision(dtype[p])
         for _ in range(warmup):
             step()
         torch.cuda.synchronize()
     for _ in range(runs):
         for p in times:
-            model.set_train_precision(p)
+            model.set_train_precision(dtype[p])
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             t0 = time.perf_counter()
@@ -145,6 +155,11 @@ def model_steps(kind, batch, height, width, runs, warmup):
                peak_memory_mib={p: round(v / 2 ** 20, 1) for p, v in peak.items()})
     rec["f32_over_f16"] = round(rec["step_ms_stats"]["f32"]["median"] / rec["step_ms_stats"]["f16"]["median"], 3)
     rec["ranges_apart"] = rec["step_ms_stats"]["f16"]["max"] < rec["step_ms_stats"]["f32"]["min"]
+    rec["f32_over_bf16"] = round(rec["step_ms_stats"]["f32"]["median"] / rec["step_ms_stats"]["bf16"]["median"], 3)
+    rec["bf16_over_f16"] = round(rec["step_ms_stats"]["bf16"]["median"] / rec["step_ms_stats"]["f16"]["median"], 3)
+    rec["bf16_ranges_apart_from_f32"] = rec["step_ms_stats"]["bf16"]["max"] < rec["step_ms_stats"]["f32"]["min"]
+    rec["bf16_within_f16_range"] = (rec["step_ms_stats"]["f16"]["min"] <= rec["step_ms_stats"]["bf16"]["median"]
+                                    <= rec["step_ms_stats"]["f16"]["max"])
     del model, opt
     torch.cuda.empty_cache()
     return rec
@@ -158,7 +173,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-steps", action="store_true")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "train_step_amp_bench.json"))
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "train_step_amp_bf16_bench.json"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     os.environ.pop("DV_TRAIN_CONV3D", None)
@@ -175,7 +190,9 @@ def main():
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
     if "steps" in rec:
-        print(json.dumps({k: {"ms": v["step_ms_stats"], "f32_over_f16": v["f32_over_f16"], "ranges_apart": v["ranges_apart"]}
+        print(json.dumps({k: {"ms": v["step_ms_stats"], "f32_over_f16": v["f32_over_f16"], "ranges_apart": v["ranges_apart"],
+                              "f32_over_bf16": v["f32_over_bf16"], "bf16_over_f16": v["bf16_over_f16"],
+                              "bf16_within_f16_range": v["bf16_within_f16_range"]}
                           for k, v in rec["steps"].items()}))
 
 
