@@ -2,13 +2,22 @@
 //
 // Same layer and fused epilogue as conv3d.hip (convbn_3d + ReLU, SceneFlow/models/submodule.py:94-97;
 // `volume * noise` prologue acv_ddim.py:260), but the MFMA stream runs on v_mfma_f32_16x16x32_f16 at
-// 16x the fp32-MFMA rate:  every fp32 activation / weight x is split exactly as x = hi + lo + O(2^-22 |x|),
+// 16x the fp32-MFMA rate:  every fp32 activation / weight x is split as x = hi + lo + O(2^-22 |x|),
 // hi = fp16(x), lo = fp16(x - hi), and   x*w  ~=  hi*hi' + hi*lo' + lo*hi'   (three MFMAs, fp32 accumulate;
-// fp16 x fp16 products are exact in fp32).  The dropped lo*lo' term and the 22-bit split are below the
-// rounding of the fp32 accumulation itself: on the 26-layer stack the split alone gives 3.5e-7 relative
-// error against float64, the reference's own fp32 CPU path 1.4e-6.  Weights are
-// pre-scaled by 2^10 and activations by 2^-2 (exact) so that lo parts stay out of the fp16 subnormal range
-// and activations up to 2.6e5 cannot overflow; the accumulator is rescaled by 2^-8 in the epilogue.
+// fp16 x fp16 products are exact in fp32).  Weights are pre-scaled by 2^10 and activations by 2^-2 (exact)
+// so that activations up to 2.6e5 cannot overflow; the accumulator is rescaled by 2^-8 in the epilogue.
+//
+// Accuracy contract.  The 22-bit split holds while lo is an fp16 NORMAL number.  lo is at most 2^-11 of the
+// scaled value v = x * in_scale * 2^-2, so that needs |v| >= 2^-3:  |x * in_scale| >= 0.5.  Below it lo is
+// subnormal, its spacing is 2^-24 whatever v is, and the pair carries an ABSOLUTE error of up to 2^-25 in v --
+// a floor of 2^-23 per activation in units of x * in_scale, 2^-23 * sum |w| per output -- instead of a relative
+// one: the median relative split error is 9e-8 at amplitude 1, 1.3e-6 at 2^-4, 2.1e-5 at 2^-8 and 3.3e-4 at
+// 2^-12.  (Weights: the same floor, 2^-35 per weight below 2^-13.)  The `volume * noise` prologue multiplies by a
+// factor in [0, 1], so the network reaches that regime.  At unit-amplitude activations the dropped lo*lo' term
+// and the split are below the rounding of the fp32 accumulation itself: there, on the 26-layer stack, the
+// split alone gives 3.5e-7 relative error against float64, the reference's own fp32 CPU path 1.4e-6
+// (profiles/NOTES_r01_r02_experiments.md section 5b).  tests/test_gpu_conv_f16x3_floor.py holds the kernel to
+// the fp32 bar plus this floor from amplitude 1 down to 2^-12 and shows where the fp32 bar alone gives way.
 //
 // GEMM view: M = 16 consecutive x of a (z,y) row, N = 16 cout, K-block (32) = 4 taps x 8 input channels:
 // lane (i = lane&15, kq = lane>>4) supplies the 8 channels of voxel i at tap slot 4*kb+kq as ONE

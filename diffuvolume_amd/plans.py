@@ -163,7 +163,13 @@ def volume_factors(volume) -> Optional[AttentionConcatVolume]:
 class Conv3dPlan:
     """A Conv3d(bias=False)[+BatchNorm3d eval][+activation] layer prepared for the
     implicit-GEMM kernel: weights repacked once on the device, BN folded to a
-    per-channel scale/bias applied in the epilogue (submodule.py:94-97)."""
+    per-channel scale/bias applied in the epilogue (submodule.py:94-97).
+
+    ``precision``: 'f32' (default; Winograd / polyphase fp32 MFMA), 'f32_direct' (fp32 MFMA, direct taps) or 'f16x3', the
+    opt-in split-fp16 kernel of the 3x3x3 stride-1 layers.  'f16x3' is as accurate as the fp32 kernels at unit-amplitude
+    activations (3.5e-7 against float64 on the 26-layer stack); its 22-bit hi + lo split holds for |x * in_scale| >= 0.5,
+    and below that every activation carries an absolute error of up to 2^-23 (2^-23 * sum |w| per output) -- see
+    csrc/conv3d_f16x3.hip."""
 
     # 3x3x3 stride-1 layers: the F(2x2x2,3x3x3) kernel (False: the in-plane F(2x2,3x3) kernel everywhere; tests / A-B runs)
     # from WINO3_MIN_CIN input channels on -- measured at batch 8 (tools/ab_wino3.py): 64 -> 64 -6.5 %, 128 -> 128 -7.5 %,

@@ -130,7 +130,8 @@ int dv_conv3d_set_c1z(int min_tiles, int segment);
 
 /* The same 3x3x3 stride-1 layer (Cout <= 32) on the fp16 matrix instruction with every fp32 operand
  * carried as hi+lo fp16 pairs: x*w ~= hi*hi' + hi*lo' + lo*hi', fp32 accumulate (csrc/conv3d_f16x3.hip).
- * Split error 2^-22 per operand, below the fp32 accumulation rounding; opt-in (DV_CONV_PRECISION=f16x3).
+ * Split error 2^-22 per operand, below the fp32 accumulation rounding, for |in * in_scale| >= 0.5; below that an
+ * absolute 2^-23 per activation (the lo half is an fp16 subnormal).  Opt-in (DV_CONV_PRECISION=f16x3).
  * Activations must stay below 2.6e5 in magnitude (fp16 range after the 2^-2 pre-scale): if one does not,
  * or is NaN, *overflow_flag (device int, may be NULL) is set to 1 and the output is not to be trusted. */
 size_t dv_conv3d_f16x3_packed_bytes(int Cin, int Cout);
