@@ -18,10 +18,11 @@ Training (``model.train()``, the reference's :424-482 branch): ``forward`` retur
 ``train3d.py``, the patch stencils on ``train_patch.py``, the hourglasses' window attention on ``train_attn.py``, the
 feature CNN and ``concatconv`` on the nn.Modules or -- with ``DV_TRAIN_NET2D=hip`` -- on ``train_net2d.py``, and
 everything else on PyTorch autograd; on CPU tensors it raises.
+The containers (convbn, BasicBlock, the hourglass), their prepared plans and the walk that runs a Sequential in training
+are ``net_blocks.py``'s, shared with the PCW flavour; the training filter is ``ddim.train_filter``.
 """
 from __future__ import annotations
 
-import math
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -30,19 +31,21 @@ from torch import nn
 
 from . import _lib
 from . import ddim
+from . import net_blocks
 from . import train3d
 from .train_tail import regress_head
-from .train_norm import bn_act
 from . import train_volume
 from .train_volume import build_concat_volume_train
 from .train_patch import patch_volume_train
 from .train_attn import window_attention_train
 from . import train_net2d
 from .head import DynamicHead
-from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, Rank1FilterPlan,
+from .net_blocks import (BasicBlockPlan, HourglassPlan, PairPlan, WindowAttention, cb2, cb3, plan_cb2, plan_seq2d,
+                         init_weights, run_plans, stack, walk)
+from .submodule import (ACT_NONE, ACT_RELU, Conv2dPlan, PlanCache, Rank1FilterPlan,
                         _dev_f32,
                         AttentionConcatVolume, build_concat_attention_volume, build_concat_volume, build_gwc_volume,
-                        check_split_overflow, default_conv_precision, patch_volume, upsample_softmax_regress, window_attention)
+                        check_split_overflow, default_conv_precision, patch_volume, upsample_softmax_regress)
 
 
 PATCH_DILATION = (1,) * 8 + (2,) * 16 + (3,) * 16      # patch_l1 / patch_l2 / patch_l3 on groups 0-7 / 8-23 / 24-39
@@ -53,50 +56,25 @@ def any_split_plan(plans) -> bool:
     return plans is not None and getattr(plans.dres0.b, "split", False)
 
 
-
-# --------------------------------------------------------------------------------------
-# parameter containers (names = reference state_dict keys)
-# --------------------------------------------------------------------------------------
-def _cb2(cin, cout, k, stride, pad, dil):
-    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, dil if dil > 1 else pad, dil, bias=False),
-                         nn.BatchNorm2d(cout))
+# the ReLU flavour of net_blocks' containers and plans, under the names tests, tools and oracle/ import
+_cb3 = cb3
+_WindowAttention = WindowAttention
 
 
-def _cb3(cin, cout, k, stride, pad):
-    return nn.Sequential(nn.Conv3d(cin, cout, k, stride, pad, bias=False), nn.BatchNorm3d(cout))
+def _train_window_attention(ab: WindowAttention, x: torch.Tensor) -> torch.Tensor:
+    """attention_block.forward (SceneFlow/models/submodule.py:398-429) in training on the route of `train_attn`
+    (DV_TRAIN_ATTN: the fused HIP forward and backward, or the PyTorch statement)."""
+    return window_attention_train(x, ab.qkv_3d.weight, ab.qkv_3d.bias, ab.final1x1.weight, ab.final1x1.bias, ab.num_heads)
 
 
-class _ResBlock2d(nn.Module):
-    """BasicBlock of the 2-D feature CNN (SceneFlow/models/submodule.py:307-330)."""
+class Hourglass(net_blocks.Hourglass):
+    """3-D encoder/decoder with skip convs and bottleneck window attention (acv_ddim.py:56-93)."""
 
-    def __init__(self, cin, planes, stride, downsample, pad, dil):
-        super().__init__()
-        self.conv1 = nn.Sequential(_cb2(cin, planes, 3, stride, pad, dil), nn.ReLU(inplace=True))
-        self.conv2 = _cb2(planes, planes, 3, 1, pad, dil)
-        self.downsample = downsample
-
-    def forward(self, x):
-        y = self.conv2(self.conv1(x))
-        return y + (x if self.downsample is None else self.downsample(x))
+    def __init__(self, c: int):
+        super().__init__(c, "relu", heads=16, attention=_train_window_attention)
 
 
-def _plan_cb2(seq: nn.Sequential, act: int) -> Conv2dPlan:
-    """convbn 2-D (Conv2d + BatchNorm2d, submodule.py:21-24 analogue) -> fused plan (stride 1 or 2)."""
-    conv, bn = seq[0], seq[1]
-    return Conv2dPlan(conv.weight, (bn.weight, bn.bias, bn.running_mean, bn.running_var), dilation=conv.dilation[0],
-                      act=act, eps=bn.eps, stride=conv.stride[0])
-
-
-class _ResBlock2dPlan:
-    """BasicBlock: convbn+ReLU, convbn, `out += x` (x through the 1x1 downsample when shape changes)."""
-
-    def __init__(self, blk: _ResBlock2d):
-        self.conv1 = _plan_cb2(blk.conv1[0], ACT_RELU)
-        self.conv2 = _plan_cb2(blk.conv2, ACT_NONE)
-        self.down = None if blk.downsample is None else _plan_cb2(blk.downsample, ACT_NONE)
-
-    def __call__(self, x):
-        return self.conv2(self.conv1(x), residual=x if self.down is None else self.down(x))
+_HourglassPlan = HourglassPlan
 
 
 class FeatureExtraction(PlanCache, nn.Module):
@@ -105,31 +83,31 @@ class FeatureExtraction(PlanCache, nn.Module):
 
     def __init__(self):
         super().__init__()
-        self.inplanes = 32
-        self.firstconv = nn.Sequential(_cb2(3, 32, 3, 2, 1, 1), nn.ReLU(inplace=True),
-                                       _cb2(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True),
-                                       _cb2(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True))
-        self.layer1 = self._stack(32, 3, 1, 1, 1)
-        self.layer2 = self._stack(64, 16, 2, 1, 1)
-        self.layer3 = self._stack(128, 3, 1, 1, 1)
-        self.layer4 = self._stack(128, 3, 1, 1, 2)
-
-    def _stack(self, planes, blocks, stride, pad, dil):
-        down = None
-        if stride != 1 or self.inplanes != planes:
-            down = nn.Sequential(nn.Conv2d(self.inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
-        layers = [_ResBlock2d(self.inplanes, planes, stride, down, pad, dil)]
-        self.inplanes = planes
-        layers += [_ResBlock2d(planes, planes, 1, None, pad, dil) for _ in range(1, blocks)]
-        return nn.Sequential(*layers)
+        self.firstconv = nn.Sequential(cb2(3, 32, 3, 2, 1, 1), nn.ReLU(inplace=True),
+                                       cb2(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True),
+                                       cb2(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True))
+        self.layer1 = stack(32, 32, 3, 1, 1, 1, "relu")
+        self.layer2 = stack(32, 64, 16, 2, 1, 1, "relu")
+        self.layer3 = stack(64, 128, 3, 1, 1, 1, "relu")
+        self.layer4 = stack(128, 128, 3, 1, 1, 2, "relu")
 
     def _build_plans(self, slot):
         if slot == train_net2d.SLOT:
             return train_net2d.build_plans(self)
         with torch.no_grad():
-            first = [_plan_cb2(self.firstconv[i], ACT_RELU) for i in (0, 2, 4)]
-            stacks = [[_ResBlock2dPlan(b) for b in getattr(self, n)] for n in ("layer1", "layer2", "layer3", "layer4")]
-        return first, stacks
+            p = {"firstconv": plan_seq2d(self.firstconv)}
+            for n in ("layer1", "layer2", "layer3", "layer4"):
+                p[n] = [BasicBlockPlan(b, down_first=False) for b in getattr(self, n)]
+        return p
+
+    def _graph(self, x, stack, head):
+        """The network, once for its three routes: ``stack(name, x)`` runs a layer of BasicBlocks, ``head(name, x)`` a
+        plain Sequential."""
+        x = stack("layer1", head("firstconv", x))
+        l2 = stack("layer2", x)
+        l3 = stack("layer3", l2)
+        l4 = stack("layer4", l3)
+        return {"gwc_feature": torch.cat((l2, l3, l4), dim=1)}
 
     def forward(self, x):
         if not x.is_cuda:
@@ -137,177 +115,41 @@ class FeatureExtraction(PlanCache, nn.Module):
         if self.training and train_net2d.route() == "hip":
             # training on the HIP route: convolutions on train2d's kernels, BatchNorm2d + ReLU + skip on train_norm's
             n = train_net2d.Net2d(self)
-            x = n.stack(self.layer1, n.seq(self.firstconv, x))
-            l2 = n.stack(self.layer2, x)
-            l3 = n.stack(self.layer3, l2)
-            l4 = n.stack(self.layer4, l3)
-            return {"gwc_feature": torch.cat((l2, l3, l4), dim=1)}
+            return self._graph(x, lambda k, t: n.stack(getattr(self, k), t), lambda k, t: n.seq(getattr(self, k), t))
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
-            x = self.layer1(self.firstconv(x))          # training / autograd: the plain PyTorch modules, on the GPU
-            l2 = self.layer2(x)
-            l3 = self.layer3(l2)
-            l4 = self.layer4(l3)
-            return {"gwc_feature": torch.cat((l2, l3, l4), dim=1)}
-        first, stacks = self.prepare(check_weights=True)
+            module = lambda k, t: getattr(self, k)(t)       # training / autograd: the plain PyTorch modules, on the GPU
+            return self._graph(x, module, module)
+        p = self.prepare(check_weights=True)
+        plan = lambda k, t: run_plans(p[k], t)
         with torch.no_grad():
-            for p in first:
-                x = p(x)
-            outs = []
-            for stack in stacks:
-                for blk in stack:
-                    x = blk(x)
-                outs.append(x)
-        return {"gwc_feature": torch.cat(outs[1:], dim=1)}
-
-
-class _WindowAttention(nn.Module):
-    """Parameters of attention_block (submodule.py:383-396)."""
-
-    def __init__(self, channels: int, num_heads: int):
-        super().__init__()
-        self.num_heads = num_heads
-        self.qkv_3d = nn.Linear(channels, channels * 3, bias=True)
-        self.final1x1 = nn.Conv3d(channels, channels, 1)
-
-
-class Hourglass(nn.Module):
-    """3-D encoder/decoder with skip convs and bottleneck window attention (acv_ddim.py:56-93)."""
-
-    def __init__(self, c: int):
-        super().__init__()
-        self.conv1 = nn.Sequential(_cb3(c, 2 * c, 3, 2, 1), nn.ReLU(inplace=True))
-        self.conv2 = nn.Sequential(_cb3(2 * c, 2 * c, 3, 1, 1), nn.ReLU(inplace=True))
-        self.conv3 = nn.Sequential(_cb3(2 * c, 4 * c, 3, 2, 1), nn.ReLU(inplace=True))
-        self.conv4 = nn.Sequential(_cb3(4 * c, 4 * c, 3, 1, 1), nn.ReLU(inplace=True))
-        self.attention_block = _WindowAttention(4 * c, 16)
-        self.conv5 = nn.Sequential(nn.ConvTranspose3d(4 * c, 2 * c, 3, padding=1, output_padding=1, stride=2, bias=False),
-                                   nn.BatchNorm3d(2 * c))
-        self.conv6 = nn.Sequential(nn.ConvTranspose3d(2 * c, c, 3, padding=1, output_padding=1, stride=2, bias=False),
-                                   nn.BatchNorm3d(c))
-        self.redir1 = _cb3(c, c, 1, 1, 0)
-        self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
-
-    def forward(self, x):
-        """Training path (acv_ddim.py:88-93); eval runs ``_HourglassPlan``."""
-        c1 = _train_cbr(self.conv1[0], x)
-        c2 = _train_cbr(self.conv2[0], c1)
-        c3 = _train_cbr(self.conv3[0], c2)
-        c4 = _train_cbr(self.conv4[0], c3)
-        c4 = _train_window_attention(self.attention_block, c4)
-        redir = _train_cb(self.redir2, c2)
-        c5 = bn_act(self.conv5[1], train3d.conv_transpose3d_module(self.conv5[0], c4), "relu", skip=redir)
-        redir = _train_cb(self.redir1, x)
-        return bn_act(self.conv6[1], train3d.conv_transpose3d_module(self.conv6[0], c5), "relu", skip=redir)
-
-
-def _train_cb(seq: nn.Sequential, x: torch.Tensor, act: str = "none") -> torch.Tensor:
-    """convbn_3d in training: the convolution on the HIP route, BatchNorm3d (batch statistics) and the activation behind
-    it on the route of `train_norm` (DV_TRAIN_NORM: the fused HIP kernels or the PyTorch statement)."""
-    return bn_act(seq[1], train3d.conv3d_module(seq[0], x), act)
-
-
-def _train_cbr(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    return _train_cb(seq, x, "relu")
-
-
-def _train_pair(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    """convbn-ReLU-conv[bn][-ReLU] stacks (dres0 / dres1 / classif*, acv_ddim.py:200-222) in training."""
-    y = _train_cbr(seq[0], x)
-    last = seq[2]
-    if isinstance(last, nn.Sequential):
-        return _train_cb(last, y, "relu" if len(seq) > 3 else "none")
-    y = train3d.conv3d_module(last, y)
-    return F.relu(y, inplace=True) if len(seq) > 3 else y
-
-
-def _train_window_attention(ab: "_WindowAttention", x: torch.Tensor) -> torch.Tensor:
-    """attention_block.forward (SceneFlow/models/submodule.py:398-429) in training on the route of `train_attn`
-    (DV_TRAIN_ATTN: the fused HIP forward and backward, or the PyTorch statement)."""
-    return window_attention_train(x, ab.qkv_3d.weight, ab.qkv_3d.bias, ab.final1x1.weight, ab.final1x1.bias, ab.num_heads)
-
-
-# --------------------------------------------------------------------------------------
-# prepared (device-resident, BN-folded, repacked) hot-path layers
-# --------------------------------------------------------------------------------------
-def _bn_of(bn: nn.BatchNorm3d):
-    return (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-
-
-def _plan_cb3(seq: nn.Sequential, stride: int, act: int) -> Conv3dPlan:
-    return Conv3dPlan(seq[0].weight, _bn_of(seq[1]), stride=stride, act=act, eps=seq[1].eps)
-
-
-class _HourglassPlan:
-    def __init__(self, hg: Hourglass):
-        self.conv1 = _plan_cb3(hg.conv1[0], 2, ACT_RELU)
-        self.conv2 = _plan_cb3(hg.conv2[0], 1, ACT_RELU)
-        self.conv3 = _plan_cb3(hg.conv3[0], 2, ACT_RELU)
-        self.conv4 = _plan_cb3(hg.conv4[0], 1, ACT_RELU)
-        ab = hg.attention_block
-        self.heads = ab.num_heads
-        self.attn = tuple(t.detach().float().contiguous() for t in
-                          (ab.qkv_3d.weight, ab.qkv_3d.bias,
-                           ab.final1x1.weight.reshape(ab.final1x1.weight.shape[0], -1), ab.final1x1.bias))
-        # relu(BN(deconv) + BN(redir(skip))): the 1x1x1 redir convolutions ride inside the transposed convolutions
-        self.conv5 = Deconv3dPlan(hg.conv5[0].weight, _bn_of(hg.conv5[1]), act=ACT_RELU, eps=hg.conv5[1].eps,
-                                  redir=(hg.redir2[0].weight, _bn_of(hg.redir2[1])), redir_eps=hg.redir2[1].eps)
-        self.conv6 = Deconv3dPlan(hg.conv6[0].weight, _bn_of(hg.conv6[1]), act=ACT_RELU, eps=hg.conv6[1].eps,
-                                  redir=(hg.redir1[0].weight, _bn_of(hg.redir1[1])), redir_eps=hg.redir1[1].eps)
-
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        c1 = self.conv1(x)
-        c2 = self.conv2(c1)
-        c3 = self.conv3(c2)
-        c4 = self.conv4(c3)
-        c4 = window_attention(c4, *self.attn, heads=self.heads)
-        c5 = self.conv5(c4, skip=c2)                       # relu(deconv+bn + redir2(conv2))
-        return self.conv6(c5, skip=x)                      # relu(deconv+bn + redir1(x))
+            return self._graph(x, plan, plan)
 
 
 # A/B switch for tools/ and tests: False keeps the first layer of a DDIM step on the generic filtered convolution
 RANK1_FILTER = True
 
 
-class _ConvPairPlan:
-    """convbn-ReLU-conv[bn][-ReLU] stacks (dres0 / dres1 / classif*, acv_ddim.py:200-222)."""
-
-    def __init__(self, seq: nn.Sequential, relu_last: bool):
-        self.a = _plan_cb3(seq[0], 1, ACT_RELU)
-        last = seq[2]
-        if isinstance(last, nn.Sequential):
-            self.b = _plan_cb3(last, 1, ACT_RELU if relu_last else ACT_NONE)
-        else:
-            self.b = Conv3dPlan(last.weight, None, stride=1, act=ACT_NONE)
-
-    def __call__(self, x, in_scale=None, residual_self=False):
-        y = self.a(x, in_scale=in_scale)
-        return self.b(y, residual=x if residual_self else None)
-
-    def second(self, y):
-        return self.b(y)
-
-
 class _Plans:
     def __init__(self, m: "ACVNet_DDIM"):
-        self.dres0 = _ConvPairPlan(m.dres0, relu_last=True)
+        self.dres0 = PairPlan(m.dres0)
         # dres0[0] on the factors of a filtered attention-concat volume (acv_ddim.py:260, :388-390); exact-fp32 paths only
         conv0, bn0 = m.dres0[0][0], m.dres0[0][1]
         self.dres0_rank1 = None
         if default_conv_precision() in ("f32", "f32_direct") and RANK1_FILTER:
             self.dres0_rank1 = Rank1FilterPlan(conv0.weight, (bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var),
                                                act=ACT_RELU, eps=bn0.eps)
-        self.dres1 = _ConvPairPlan(m.dres1, relu_last=False)
+        self.dres1 = PairPlan(m.dres1)
         self.dres2 = _HourglassPlan(m.dres2)
         self.dres3 = _HourglassPlan(m.dres3)
-        self.classif2 = _ConvPairPlan(m.classif2, relu_last=False)
-        self.dres1_att = _ConvPairPlan(m.dres1_att_, relu_last=False)
+        self.classif2 = PairPlan(m.classif2)
+        self.dres1_att = PairPlan(m.dres1_att_)
         self.dres2_att = _HourglassPlan(m.dres2_att_)
-        self.classif_att = _ConvPairPlan(m.classif_att_, relu_last=False)
+        self.classif_att = PairPlan(m.classif_att_)
         # attention branch front: the two depth-wise (1,3,3) stencils fuse into one pass; concatconv on the 2-D kernel
         self.patch_w1 = m.patch.weight.detach().float().reshape(40, 9).contiguous()
         self.patch_w2 = torch.cat([p.weight.detach().float().reshape(-1, 9) for p in (m.patch_l1, m.patch_l2, m.patch_l3)]).contiguous()
         self.patch_dil = torch.tensor([1] * 8 + [2] * 16 + [3] * 16, dtype=torch.int32, device=self.patch_w1.device)
-        self.concat_a = _plan_cb2(m.concatconv[0], ACT_RELU)
+        self.concat_a = plan_cb2(m.concatconv[0], ACT_RELU)
         self.concat_b = Conv2dPlan(m.concatconv[2].weight, None, act=ACT_NONE)
         # the origin ACVNet has no diffusion schedule
         self.ddim = ddim.Tables(m.alphas_cumprod) if hasattr(m, "alphas_cumprod") else None
@@ -349,6 +191,34 @@ class _HipPlanMixin(PlanCache, nn.Module):
         with torch.no_grad(), torch.cuda.device(dev):
             return _Plans(self)
 
+    def _init_backbone(self, time_embedding: bool):
+        """Sub-modules under the reference's attribute names, in its construction order (acv_ddim.py:174-222,
+        acv.py:103-150), and its weight initialisation (:224-238)."""
+        def pair(cin):
+            return nn.Sequential(cb3(cin, 32, 3, 1, 1), nn.ReLU(inplace=True), cb3(32, 32, 3, 1, 1))
+
+        def classifier():
+            return nn.Sequential(cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True), nn.Conv3d(32, 1, 3, 1, 1, bias=False))
+        self.feature_extraction = FeatureExtraction()
+        self.concatconv = nn.Sequential(cb2(320, 128, 3, 1, 1, 1), nn.ReLU(inplace=True),
+                                        nn.Conv2d(128, self.concat_channels, 1, bias=False))
+        self.patch = nn.Conv3d(40, 40, (1, 3, 3), 1, (0, 1, 1), 1, groups=40, bias=False)
+        self.patch_l1 = nn.Conv3d(8, 8, (1, 3, 3), 1, (0, 1, 1), 1, groups=8, bias=False)
+        self.patch_l2 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 2, 2), 2, groups=16, bias=False)
+        self.patch_l3 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 3, 3), 3, groups=16, bias=False)
+        self.dres1_att_ = pair(40)
+        self.dres2_att_ = Hourglass(32)
+        self.classif_att_ = classifier()
+        if time_embedding:
+            self.time_embedding = DynamicHead(d_model=48)
+        self.dres0 = nn.Sequential(cb3(64, 32, 3, 1, 1), nn.ReLU(inplace=True),
+                                   cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True))
+        self.dres1 = pair(32)
+        self.dres2 = Hourglass(32)
+        self.dres3 = Hourglass(32)
+        self.classif0, self.classif1, self.classif2 = classifier(), classifier(), classifier()
+        init_weights(self)
+
 
 class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
     def __init__(self, maxdisp: int, attn_weights_only: bool = False, freeze_attn_weights: bool = False,
@@ -380,44 +250,7 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
 
         ddim.register_schedule(self, self.num_timesteps)
 
-        self.feature_extraction = FeatureExtraction()
-        self.concatconv = nn.Sequential(_cb2(320, 128, 3, 1, 1, 1), nn.ReLU(inplace=True),
-                                        nn.Conv2d(128, self.concat_channels, 1, bias=False))
-        self.patch = nn.Conv3d(40, 40, (1, 3, 3), 1, (0, 1, 1), 1, groups=40, bias=False)
-        self.patch_l1 = nn.Conv3d(8, 8, (1, 3, 3), 1, (0, 1, 1), 1, groups=8, bias=False)
-        self.patch_l2 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 2, 2), 2, groups=16, bias=False)
-        self.patch_l3 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 3, 3), 3, groups=16, bias=False)
-        self.dres1_att_ = nn.Sequential(_cb3(40, 32, 3, 1, 1), nn.ReLU(inplace=True), _cb3(32, 32, 3, 1, 1))
-        self.dres2_att_ = Hourglass(32)
-        self.classif_att_ = self._classifier()
-        self.time_embedding = DynamicHead(d_model=48)
-        self.dres0 = nn.Sequential(_cb3(64, 32, 3, 1, 1), nn.ReLU(inplace=True),
-                                   _cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True))
-        self.dres1 = nn.Sequential(_cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True), _cb3(32, 32, 3, 1, 1))
-        self.dres2 = Hourglass(32)
-        self.dres3 = Hourglass(32)
-        self.classif0 = self._classifier()
-        self.classif1 = self._classifier()
-        self.classif2 = self._classifier()
-        self._init_weights()
-
-    @staticmethod
-    def _classifier():
-        return nn.Sequential(_cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True),
-                             nn.Conv3d(32, 1, 3, 1, 1, bias=False))
-
-    def _init_weights(self):  # acv_ddim.py:224-238
-        for m in self.modules():
-            if isinstance(m, (nn.Conv2d, nn.Conv3d)) and not isinstance(m, nn.ConvTranspose3d):
-                n = m.out_channels
-                for k in m.kernel_size:
-                    n *= k
-                m.weight.data.normal_(0, math.sqrt(2.0 / n))
-            elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm3d)):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
-            elif isinstance(m, nn.Linear):
-                m.bias.data.zero_()
+        self._init_backbone(time_embedding=True)
 
     # ---- pieces of the hot path ----------------------------------------------------------
     def _time_pairs(self):
@@ -578,9 +411,9 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
         patch = patch_volume_train(gwc, self.patch.weight.reshape(40, 9),
                                    torch.cat([m.weight.reshape(-1, 9) for m in (self.patch_l1, self.patch_l2, self.patch_l3)]),
                                    PATCH_DILATION)
-        cost_attention = _train_pair(self.dres1_att_, patch)
+        cost_attention = walk(self.dres1_att_, patch)
         cost_attention = self.dres2_att_(cost_attention)
-        att_weights = _train_pair(self.classif_att_, cost_attention)
+        att_weights = walk(self.classif_att_, cost_attention)
 
         if train_net2d.route() == "hip":
             n2d = train_net2d.Net2d(self, ("concatconv.",))
@@ -603,9 +436,9 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
             if factored:
                 ac_volume = build_concat_volume_train(cl.detach(), cr.detach(), self.maxdisp // 4,
                                                       scale=p_att.detach()[:, 0])
-            cost0 = _train_pair(self.dres0, ac_volume)
-            cost0 = _train_pair(self.dres1, cost0) + cost0
-            _train_pair(self.classif2, self.dres3(self.dres2(cost0)))
+            cost0 = walk(self.dres0, ac_volume)
+            cost0 = walk(self.dres1, cost0) + cost0
+            walk(self.classif2, self.dres3(self.dres2(cost0)))
             del cost0
             if factored:
                 del ac_volume
@@ -615,22 +448,15 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
         if mask_gt is not None:
             uniform = ((torch.ones((), dtype=torch.float32, device=x_start.device) / (self.maxdisp // 4)) * 2 - 1) * self.scale
             x_start = torch.where(mask_gt.to(x_start.device).unsqueeze(1) == 0, uniform, x_start.unsqueeze(1)).squeeze(1)
-        t = torch.randint(0, self.num_timesteps, (1,), device=x_start.device).long()
-        noise = torch.randn_like(x_start)
-        with torch.no_grad():                      # `torch.tensor(noisy)` (:449): no gradient reaches time_embedding
-            noisy = (self.sqrt_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * x_start
-                     + self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * noise)
-            noisy = self.time_embedding(noisy, t)
-            noisy = torch.clamp(noisy, min=-1 * self.scale, max=self.scale)
-            noisy = ((noisy / self.scale) + 1) / 2.
-            noisy = noisy.unsqueeze(1).to(torch.float32)
+        noisy = ddim.train_filter(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.time_embedding,
+                                  self.scale, self.num_timesteps, x_start)
 
         if factored:
             ac_volume = build_concat_volume_train(cl, cr, self.maxdisp // 4, scale=(p_att * noisy)[:, 0])
         else:
             ac_volume = ac_volume * noisy
-        cost0 = _train_pair(self.dres0, ac_volume)
-        cost0 = _train_pair(self.dres1, cost0) + cost0
+        cost0 = walk(self.dres0, ac_volume)
+        cost0 = walk(self.dres1, cost0) + cost0
         out1 = self.dres2(cost0)
         out2 = self.dres3(out1)
 
@@ -638,9 +464,9 @@ class ACVNet_DDIM(train3d.TrainPrecision, _HipPlanMixin):
 
         # the fused tail with its HIP backward (train_tail.py; DV_TRAIN_TAIL)
         pred_attention = regress_head(att_weights, size)
-        pred0 = regress_head(_train_pair(self.classif0, cost0), size)
-        pred1 = regress_head(_train_pair(self.classif1, out1), size)
-        pred2 = regress_head(_train_pair(self.classif2, out2), size)
+        pred0 = regress_head(walk(self.classif0, cost0), size)
+        pred1 = regress_head(walk(self.classif1, out1), size)
+        pred2 = regress_head(walk(self.classif2, out2), size)
         return [pred_attention, pred0, pred1, pred2]
 
     def forward(self, left, right, used, disp, mask_gt=None):
@@ -669,25 +495,7 @@ class ACVNet(_HipPlanMixin):
             raise ValueError("ACVNet on the HIP path: maxdisp == 192")
         self.maxdisp, self.attn_weights_only, self.freeze_attn_weights = maxdisp, attn_weights_only, freeze_attn_weights
         self.num_groups, self.concat_channels = 40, 32
-        self.feature_extraction = FeatureExtraction()
-        self.concatconv = nn.Sequential(_cb2(320, 128, 3, 1, 1, 1), nn.ReLU(inplace=True),
-                                        nn.Conv2d(128, self.concat_channels, 1, bias=False))
-        self.patch = nn.Conv3d(40, 40, (1, 3, 3), 1, (0, 1, 1), 1, groups=40, bias=False)
-        self.patch_l1 = nn.Conv3d(8, 8, (1, 3, 3), 1, (0, 1, 1), 1, groups=8, bias=False)
-        self.patch_l2 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 2, 2), 2, groups=16, bias=False)
-        self.patch_l3 = nn.Conv3d(16, 16, (1, 3, 3), 1, (0, 3, 3), 3, groups=16, bias=False)
-        self.dres1_att_ = nn.Sequential(_cb3(40, 32, 3, 1, 1), nn.ReLU(inplace=True), _cb3(32, 32, 3, 1, 1))
-        self.dres2_att_ = Hourglass(32)
-        self.classif_att_ = ACVNet_DDIM._classifier()
-        self.dres0 = nn.Sequential(_cb3(64, 32, 3, 1, 1), nn.ReLU(inplace=True),
-                                   _cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True))
-        self.dres1 = nn.Sequential(_cb3(32, 32, 3, 1, 1), nn.ReLU(inplace=True), _cb3(32, 32, 3, 1, 1))
-        self.dres2 = Hourglass(32)
-        self.dres3 = Hourglass(32)
-        self.classif0 = ACVNet_DDIM._classifier()
-        self.classif1 = ACVNet_DDIM._classifier()
-        self.classif2 = ACVNet_DDIM._classifier()
-        ACVNet_DDIM._init_weights(self)
+        self._init_backbone(time_embedding=False)
 
     attention_logits = ACVNet_DDIM.attention_logits
     attention_concat_volume = ACVNet_DDIM.attention_concat_volume

@@ -109,6 +109,23 @@ def noise_prepare(time_embedding, x_t: torch.Tensor, t: Optional[torch.Tensor], 
     return n01, n01f
 
 
+def train_filter(sqrt_alphas_cumprod: torch.Tensor, sqrt_one_minus_alphas_cumprod: torch.Tensor, time_embedding, scale: float,
+                 num_timesteps: int, x_start: torch.Tensor) -> torch.Tensor:
+    """The volume filter of a training step of ACV and PCW (acv_ddim.py:441-451, pwcnet_ddim.py:661-669): draws
+    ``t = torch.randint(0, T, (1,))`` and then q_sample's ``torch.randn_like`` (in that order), q_sample with the model's
+    schedule buffers, the time embedding, clamp, [0,1] -> [B,1,D,h,w] float32.  No gradient reaches ``time_embedding``
+    (the reference's ``torch.tensor(noisy)``)."""
+    t = torch.randint(0, num_timesteps, (1,), device=x_start.device).long()
+    noise = torch.randn_like(x_start)
+    with torch.no_grad():
+        noisy = (sqrt_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * x_start
+                 + sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * noise)
+        noisy = time_embedding(noisy, t)
+        noisy = torch.clamp(noisy, min=-1 * scale, max=scale)
+        noisy = ((noisy / scale) + 1) / 2.
+        return noisy.unsqueeze(1).to(torch.float32)
+
+
 def ddim_update(disp, used, n01, eps, fill, mask, ens, coef: _lib.DvDdimCoef, *, unc=None, coords0=None,
                 want_pred_noise=False):
     """``dv_ddim_step``: two-hot x_start of ``disp``, renewal mask, ensemble and the next state -> (x_start fp32,

@@ -20,243 +20,122 @@ Training (``model.train()``, the reference's :643-735 branch): ``forward`` retur
 Mish behind them on ``train_norm.py``, the 2-D convolutions of ``refinenet3`` on ``train2d.py`` and the rest (feature
 CNN, BatchNorm2d and its Mish, the resize of ``finetune_feature``; ``dispupsample`` in float64) on PyTorch autograd -- with
 ``DV_TRAIN_NET2D=hip`` the feature CNN, BatchNorm2d + Mish and the resize run on ``train_net2d.py``; on CPU tensors it raises.
+The containers (convbn, BasicBlock, the hourglass, ``Mish``), their prepared plans and the walk that runs a Sequential in
+training are ``net_blocks.py``'s, shared with the ACV flavour; the training filter is ``ddim.train_filter``.
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, ddim, train2d, train3d, train_net2d
-from .acv_ddim import ProbVolumeHandle, _bn_of, _plan_cb3
+from . import _lib, ddim, net_blocks, train2d, train3d, train_net2d
+from .acv_ddim import ProbVolumeHandle
 from .head import DynamicHead
+from .net_blocks import (BasicBlockPlan, Mish, PairPlan, cb2, cb3, deconv_plan, head2d, init_weights, plan_cb2, plan_cb3,
+                         plan_seq2d, run_plans, stack, walk)
 from .plans import settle_build
 from .train_tail import regress_head
 from .train_refine import warp_corr_train
-from .train_norm import bn_act
-from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, Deconv3dPlan, PlanCache, _dev_f32, build_concat_volume,
+from .train_norm import act_statement
+from .submodule import (ACT_MISH, ACT_NONE, Conv2dPlan, Conv3dPlan, PlanCache, _dev_f32, build_concat_volume,
                         build_gwc_volume, check_split_overflow, refine_inputs,
                         upsample_softmax_regress)
 
 
-class Mish(nn.Module):
-    """x * tanh(softplus(x)) (KITTI12/models/submodule.py:11-18)."""
-
-    def forward(self, x):
-        return x * torch.tanh(F.softplus(x))
-
-
-def fmish(x):
-    """FMish (KITTI12/models/submodule.py:177-189)."""
-    return x * torch.tanh(F.softplus(x))
-
-
-def _train_seq(seq: nn.Module, x: torch.Tensor, act: str = "none", skip: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """A Sequential of the training graph, then `+ skip` and `act` ("none" / "mish"): 3-D convolutions on `train3d`, 2-D
-    ones on `train2d` (refinenet3 only).  A BatchNorm3d goes to `train_norm.bn_act` together with what follows it -- the
-    Mish behind it in the walk, or the caller's skip and activation when it ends the walk (the hourglass tails) -- so that
-    DV_TRAIN_NORM=hip runs them as one kernel, and with DV_TRAIN_NET2D=hip a BatchNorm2d (refinenet3) goes to
-    `train_net2d.bn_act2d` the same way; everything else (a Mish behind something else) stays PyTorch."""
-    mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
-    i = 0
-    while i < len(mods):
-        m = mods[i]
-        last = i == len(mods) - 1
-        a, s, step = (act, skip, 1) if last else ("none", None, 1)
-        if not last and isinstance(mods[i + 1], Mish) and (i + 2 < len(mods) or (act == "none" and skip is None)):
-            a, s, step = "mish", None, 2                       # m and the Mish behind it as one statement
-        if isinstance(m, nn.Sequential):
-            x = _train_seq(m, x, a, s)
-        elif isinstance(m, nn.BatchNorm3d):
-            x = bn_act(m, x, a, s)
-        elif isinstance(m, nn.BatchNorm2d) and train_net2d.route() == "hip":
-            x = train_net2d.bn_act2d(m, x, a, s)
-        else:
-            if isinstance(m, nn.ConvTranspose3d):
-                x = train3d.conv_transpose3d_module(m, x)
-            elif isinstance(m, nn.Conv3d):
-                x = train3d.conv3d_module(m, x)
-            elif isinstance(m, nn.Conv2d):
-                x = train2d.conv2d_module(m, x)
-            else:
-                x = m(x)
-            if s is not None:
-                x = x + s
-            if a == "mish":
-                x = fmish(x)
-            elif a != "none":
-                raise ValueError(f"act must be 'none' or 'mish', got {a!r}")
-        i += step
-    return x
-
-
-def _cb2(cin, cout, k, stride, pad, dil):
-    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, dil if dil > 1 else pad, dil, bias=False),
-                         nn.BatchNorm2d(cout))
-
-
-def _cb3(cin, cout, k, stride, pad):
-    return nn.Sequential(nn.Conv3d(cin, cout, k, stride, pad, bias=False), nn.BatchNorm3d(cout))
-
-
-class _Block2d(nn.Module):
-    """BasicBlock with Mish (KITTI12/models/submodule.py:192-215)."""
-
-    def __init__(self, cin, planes, stride, downsample, pad, dil):
-        super().__init__()
-        self.conv1 = nn.Sequential(_cb2(cin, planes, 3, stride, pad, dil), Mish())
-        self.conv2 = _cb2(planes, planes, 3, 1, pad, dil)
-        self.downsample = downsample
-
-    def forward(self, x):
-        y = self.conv2(self.conv1(x))
-        return y + (x if self.downsample is None else self.downsample(x))
-
-
-class _Stacker:
-    inplanes: int
-
-    def _stack(self, planes, blocks, stride, pad, dil):
-        down = None
-        if stride != 1 or self.inplanes != planes:
-            down = nn.Sequential(nn.Conv2d(self.inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
-        layers = [_Block2d(self.inplanes, planes, stride, down, pad, dil)]
-        self.inplanes = planes
-        layers += [_Block2d(planes, planes, 1, None, pad, dil) for _ in range(1, blocks)]
-        return nn.Sequential(*layers)
-
-
-def _head2d(cin, mid, cout):
-    return nn.Sequential(_cb2(cin, mid, 3, 1, 1, 1), Mish(), nn.Conv2d(mid, cout, 1, bias=False))
-
-
-class FeatureExtraction(PlanCache, nn.Module, _Stacker):
+class FeatureExtraction(PlanCache, nn.Module):
     """Multi-scale 2-D feature CNN (pwcnet_ddim.py:12-128): gw1..gw4 at 1/4..1/32, concat features,
     refinement feature.  On the GPU (eval) every convolution runs on the 2-D HIP kernel."""
+
+    STACKS = ("layer1", "layer2", "layer3", "layer4", "layer5", "layer7", "layer9")
 
     def __init__(self, concat_feature=False, concat_feature_channel=12):
         super().__init__()
         self.concat_feature = concat_feature
-        self.inplanes = 32
-        self.firstconv = nn.Sequential(_cb2(3, 32, 3, 2, 1, 1), Mish(), _cb2(32, 32, 3, 1, 1, 1), Mish(),
-                                       _cb2(32, 32, 3, 1, 1, 1), Mish())
-        self.layer1 = self._stack(32, 3, 1, 1, 1)
-        self.layer2 = self._stack(64, 16, 2, 1, 1)
-        self.layer3 = self._stack(128, 3, 1, 1, 1)
-        self.layer4 = self._stack(128, 3, 1, 1, 2)
-        self.layer5 = self._stack(192, 3, 2, 1, 1)
-        self.layer7 = self._stack(256, 3, 2, 1, 1)
-        self.layer9 = self._stack(512, 3, 2, 1, 1)
-        self.gw2 = _head2d(192, 320, 320)
-        self.gw3 = _head2d(256, 320, 320)
-        self.gw4 = _head2d(512, 320, 320)
-        self.layer11 = _head2d(320, 320, 320)
-        self.layer_refine = nn.Sequential(_cb2(320, 128, 3, 1, 1, 1), Mish(), _cb2(128, 32, 1, 1, 0, 1), Mish())
+        self.firstconv = nn.Sequential(cb2(3, 32, 3, 2, 1, 1), Mish(), cb2(32, 32, 3, 1, 1, 1), Mish(),
+                                       cb2(32, 32, 3, 1, 1, 1), Mish())
+        self.layer1 = stack(32, 32, 3, 1, 1, 1, "mish")
+        self.layer2 = stack(32, 64, 16, 2, 1, 1, "mish")
+        self.layer3 = stack(64, 128, 3, 1, 1, 1, "mish")
+        self.layer4 = stack(128, 128, 3, 1, 1, 2, "mish")
+        self.layer5 = stack(128, 192, 3, 2, 1, 1, "mish")
+        self.layer7 = stack(192, 256, 3, 2, 1, 1, "mish")
+        self.layer9 = stack(256, 512, 3, 2, 1, 1, "mish")
+        self.gw2 = head2d(192, 320, 320)
+        self.gw3 = head2d(256, 320, 320)
+        self.gw4 = head2d(512, 320, 320)
+        self.layer11 = head2d(320, 320, 320)
+        self.layer_refine = nn.Sequential(cb2(320, 128, 3, 1, 1, 1), Mish(), cb2(128, 32, 1, 1, 0, 1), Mish())
         if concat_feature:
-            self.lastconv = _head2d(320, 128, concat_feature_channel)
-            self.concat2 = _head2d(192, 128, concat_feature_channel)
-            self.concat3 = _head2d(256, 128, concat_feature_channel)
-            self.concat4 = _head2d(512, 128, concat_feature_channel)
+            self.lastconv = head2d(320, 128, concat_feature_channel)
+            self.concat2 = head2d(192, 128, concat_feature_channel)
+            self.concat3 = head2d(256, 128, concat_feature_channel)
+            self.concat4 = head2d(512, 128, concat_feature_channel)
 
     # ---- HIP plans (csrc/conv2d.hip: BN / Mish / residual fused), rebuilt when the parameters change ----
     def _build_plans(self, slot):
         if slot == train_net2d.SLOT:
             return train_net2d.build_plans(self)
-
-        def head(seq):          # convbn + Mish + Conv2d 1x1
-            return (_plan_cb2(seq[0], ACT_MISH), Conv2dPlan(seq[2].weight, None, act=ACT_NONE))
+        heads = ("gw2", "gw3", "gw4", "layer11") + (("lastconv", "concat2", "concat3", "concat4") if self.concat_feature else ())
         with torch.no_grad():
-            p = {"first": [_plan_cb2(self.firstconv[i], ACT_MISH) for i in (0, 2, 4)]}
-            for n in ("layer1", "layer2", "layer3", "layer4", "layer5", "layer7", "layer9"):
-                p[n] = [_Block2dPlan(b) for b in getattr(self, n)]
-            for n in ("gw2", "gw3", "gw4", "layer11") + (("lastconv", "concat2", "concat3", "concat4") if self.concat_feature else ()):
-                p[n] = head(getattr(self, n))
-            p["refine"] = (_plan_cb2(self.layer_refine[0], ACT_MISH), _plan_cb2(self.layer_refine[2], ACT_MISH))
+            p = {"firstconv": plan_seq2d(self.firstconv)}
+            for n in self.STACKS:
+                p[n] = [BasicBlockPlan(b) for b in getattr(self, n)]
+            for n in heads + ("layer_refine",):
+                p[n] = plan_seq2d(getattr(self, n))
         return p
+
+    def _graph(self, x, stack, head):
+        """The network, once for its three routes: ``stack(name, x)`` runs a layer of BasicBlocks, ``head(name, x)`` a
+        plain Sequential (firstconv, the gw / concat heads, layer_refine)."""
+        x = stack("layer1", head("firstconv", x))
+        l2 = stack("layer2", x)
+        l3 = stack("layer3", l2)
+        l4 = stack("layer4", l3)
+        l5 = stack("layer5", l4)
+        l6 = stack("layer7", l5)
+        l7 = stack("layer9", l6)
+        fc = torch.cat((l2, l3, l4), dim=1)
+        out = {"gw1": head("layer11", fc), "gw2": head("gw2", l5), "gw3": head("gw3", l6), "gw4": head("gw4", l7)}
+        if self.concat_feature:
+            out.update(concat_feature1=head("lastconv", fc), finetune_feature=head("layer_refine", fc),
+                       concat_feature2=head("concat2", l5), concat_feature3=head("concat3", l6),
+                       concat_feature4=head("concat4", l7))
+        return out
 
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.DiffuVolumeError(f"input is on {x.device}: the feature CNN runs on the MI355X (no CPU fallback)")
         if self.training and train_net2d.route() == "hip":
-            return self._forward_train_hip(x)
+            n = train_net2d.Net2d(self)                     # training on the HIP route of `train_net2d`
+            return self._graph(x, lambda k, t: n.stack(getattr(self, k), t), lambda k, t: n.seq(getattr(self, k), t))
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             return self._forward_modules(x)
         p = self.prepare(check_weights=True)
-        def run(plans, t):
-            for q in plans:
-                t = q(t)
-            return t
+        plan = lambda k, t: run_plans(p[k], t)
         with torch.no_grad():
-            for q in p["first"]:
-                x = q(x)
-            x = run(p["layer1"], x)
-            l2 = run(p["layer2"], x)
-            l3 = run(p["layer3"], l2)
-            l4 = run(p["layer4"], l3)
-            l5 = run(p["layer5"], l4)
-            l6 = run(p["layer7"], l5)
-            l7 = run(p["layer9"], l6)
-            fc = torch.cat((l2, l3, l4), dim=1)
-            out = {"gw1": run(p["layer11"], fc), "gw2": run(p["gw2"], l5), "gw3": run(p["gw3"], l6), "gw4": run(p["gw4"], l7)}
-            if self.concat_feature:
-                out.update(concat_feature1=run(p["lastconv"], fc), finetune_feature=run(p["refine"], fc),
-                           concat_feature2=run(p["concat2"], l5), concat_feature3=run(p["concat3"], l6),
-                           concat_feature4=run(p["concat4"], l7))
-        return out
-
-    def _forward_train_hip(self, x):
-        """The same graph in training on the HIP route of `train_net2d` (DV_TRAIN_NET2D=hip)."""
-        n = train_net2d.Net2d(self)
-        x = n.stack(self.layer1, n.seq(self.firstconv, x))
-        l2 = n.stack(self.layer2, x)
-        l3 = n.stack(self.layer3, l2)
-        l4 = n.stack(self.layer4, l3)
-        l5 = n.stack(self.layer5, l4)
-        l6 = n.stack(self.layer7, l5)
-        l7 = n.stack(self.layer9, l6)
-        fc = torch.cat((l2, l3, l4), dim=1)
-        out = {"gw1": n.seq(self.layer11, fc), "gw2": n.seq(self.gw2, l5), "gw3": n.seq(self.gw3, l6),
-               "gw4": n.seq(self.gw4, l7)}
-        if self.concat_feature:
-            out.update(concat_feature1=n.seq(self.lastconv, fc), finetune_feature=n.seq(self.layer_refine, fc),
-                       concat_feature2=n.seq(self.concat2, l5), concat_feature3=n.seq(self.concat3, l6),
-                       concat_feature4=n.seq(self.concat4, l7))
-        return out
+            return self._graph(x, plan, plan)
 
     def _forward_modules(self, x):
-        """The same graph on the plain nn.Modules (training / autograd on the GPU; reference for the tests)."""
-        x = self.layer1(self.firstconv(x))
-        l2 = self.layer2(x)
-        l3 = self.layer3(l2)
-        l4 = self.layer4(l3)
-        l5 = self.layer5(l4)
-        l6 = self.layer7(l5)
-        l7 = self.layer9(l6)
-        fc = torch.cat((l2, l3, l4), dim=1)
-        out = {"gw1": self.layer11(fc), "gw2": self.gw2(l5), "gw3": self.gw3(l6), "gw4": self.gw4(l7)}
-        if self.concat_feature:
-            out.update(concat_feature1=self.lastconv(fc), finetune_feature=self.layer_refine(fc),
-                       concat_feature2=self.concat2(l5), concat_feature3=self.concat3(l6),
-                       concat_feature4=self.concat4(l7))
-        return out
+        """The graph on the plain nn.Modules (training / autograd on the GPU; reference for the tests)."""
+        module = lambda k, t: getattr(self, k)(t)
+        return self._graph(x, module, module)
 
 
-class RefineNet(nn.Module, _Stacker):
+class RefineNet(nn.Module):
     """refinenet_version3 (pwcnet_ddim.py:251-306): dilated 2-D residual stack -> disparity residual."""
 
     def __init__(self, in_channels):
         super().__init__()
-        self.inplanes = 128
-        self.conv1 = nn.Sequential(_cb2(in_channels, 128, 3, 1, 1, 1), Mish())
-        self.conv2 = nn.Sequential(_cb2(128, 128, 3, 1, 1, 1), Mish())
-        self.conv3 = nn.Sequential(_cb2(128, 128, 3, 1, 2, 2), Mish())
-        self.conv4 = nn.Sequential(_cb2(128, 128, 3, 1, 4, 4), Mish())
-        self.conv5 = self._stack(96, 1, 1, 1, 8)
-        self.conv6 = self._stack(64, 1, 1, 1, 16)
-        self.conv7 = self._stack(32, 1, 1, 1, 1)
+        self.conv1 = nn.Sequential(cb2(in_channels, 128, 3, 1, 1, 1), Mish())
+        self.conv2 = nn.Sequential(cb2(128, 128, 3, 1, 1, 1), Mish())
+        self.conv3 = nn.Sequential(cb2(128, 128, 3, 1, 2, 2), Mish())
+        self.conv4 = nn.Sequential(cb2(128, 128, 3, 1, 4, 4), Mish())
+        self.conv5 = stack(128, 96, 1, 1, 1, 8, "mish")
+        self.conv6 = stack(96, 64, 1, 1, 1, 16, "mish")
+        self.conv7 = stack(64, 32, 1, 1, 1, 1, "mish")
         self.conv8 = nn.Conv2d(32, 1, 3, 1, 1, bias=False)
 
     def forward(self, x, disp):
@@ -265,12 +144,14 @@ class RefineNet(nn.Module, _Stacker):
         return disp + x
 
     def train_forward(self, x, disp):
-        """pwcnet_ddim.py:292-306 in training: every convolution on `train2d`."""
-        x = _train_seq(nn.Sequential(self.conv1, self.conv2, self.conv3, self.conv4), x)
-        for blk in (self.conv5[0], self.conv6[0], self.conv7[0]):        # BasicBlock (submodule.py:192-215)
-            skip = x if blk.downsample is None else _train_seq(blk.downsample, x)
-            x = _train_seq(blk.conv2, _train_seq(blk.conv1, x), "none", skip)
-        return disp + _train_seq(self.conv8, x)
+        """pwcnet_ddim.py:292-306 in training: every convolution on `train2d`; with DV_TRAIN_NET2D=hip a BatchNorm2d runs
+        on `train_net2d.bn_act2d` with the Mish or the block's skip behind it."""
+        n = train_net2d.Net2d(conv2d=train2d.conv2d_module)
+        for m in (self.conv1, self.conv2, self.conv3, self.conv4):
+            x = n.seq(m, x)
+        for m in (self.conv5, self.conv6, self.conv7):
+            x = n.stack(m, x)
+        return disp + n.seq(self.conv8, x)
 
 
 class HourglassUp(nn.Module):
@@ -279,88 +160,47 @@ class HourglassUp(nn.Module):
     def __init__(self, c):
         super().__init__()
         self.conv1 = nn.Conv3d(c, 2 * c, 3, 2, 1, bias=False)
-        self.conv2 = nn.Sequential(_cb3(2 * c, 2 * c, 3, 1, 1), Mish())
+        self.conv2 = nn.Sequential(cb3(2 * c, 2 * c, 3, 1, 1), Mish())
         self.conv3 = nn.Conv3d(2 * c, 4 * c, 3, 2, 1, bias=False)
-        self.conv4 = nn.Sequential(_cb3(4 * c, 4 * c, 3, 1, 1), Mish())
+        self.conv4 = nn.Sequential(cb3(4 * c, 4 * c, 3, 1, 1), Mish())
         self.conv5 = nn.Conv3d(4 * c, 4 * c, 3, 2, 1, bias=False)
-        self.conv6 = nn.Sequential(_cb3(4 * c, 4 * c, 3, 1, 1), Mish())
+        self.conv6 = nn.Sequential(cb3(4 * c, 4 * c, 3, 1, 1), Mish())
         self.conv7 = nn.Sequential(nn.ConvTranspose3d(4 * c, 4 * c, 3, padding=1, output_padding=1, stride=2, bias=False),
                                    nn.BatchNorm3d(4 * c))
         self.conv8 = nn.Sequential(nn.ConvTranspose3d(4 * c, 2 * c, 3, padding=1, output_padding=1, stride=2, bias=False),
                                    nn.BatchNorm3d(2 * c))
         self.conv9 = nn.Sequential(nn.ConvTranspose3d(2 * c, c, 3, padding=1, output_padding=1, stride=2, bias=False),
                                    nn.BatchNorm3d(c))
-        self.combine1 = nn.Sequential(_cb3(4 * c, 2 * c, 3, 1, 1), Mish())
-        self.combine2 = nn.Sequential(_cb3(6 * c, 4 * c, 3, 1, 1), Mish())
-        self.combine3 = nn.Sequential(_cb3(6 * c, 4 * c, 3, 1, 1), Mish())
-        self.redir1 = _cb3(c, c, 1, 1, 0)
-        self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
-        self.redir3 = _cb3(4 * c, 4 * c, 1, 1, 0)
+        self.combine1 = nn.Sequential(cb3(4 * c, 2 * c, 3, 1, 1), Mish())
+        self.combine2 = nn.Sequential(cb3(6 * c, 4 * c, 3, 1, 1), Mish())
+        self.combine3 = nn.Sequential(cb3(6 * c, 4 * c, 3, 1, 1), Mish())
+        self.redir1 = cb3(c, c, 1, 1, 0)
+        self.redir2 = cb3(2 * c, 2 * c, 1, 1, 0)
+        self.redir3 = cb3(4 * c, 4 * c, 1, 1, 0)
 
     def forward(self, x, f4, f5, f6):
         """Training path (pwcnet_ddim.py:181-205); eval runs ``_HourglassUpPlan``."""
-        c2 = _train_seq(self.conv2, _train_seq(self.combine1, torch.cat((_train_seq(self.conv1, x), f4), dim=1)))
-        c4 = _train_seq(self.conv4, _train_seq(self.combine2, torch.cat((_train_seq(self.conv3, c2), f5), dim=1)))
-        c6 = _train_seq(self.conv6, _train_seq(self.combine3, torch.cat((_train_seq(self.conv5, c4), f6), dim=1)))
-        c7 = _train_seq(self.conv7, c6, "mish", skip=_train_seq(self.redir3, c4))
-        c8 = _train_seq(self.conv8, c7, "mish", skip=_train_seq(self.redir2, c2))
-        return _train_seq(self.conv9, c8, "mish", skip=_train_seq(self.redir1, x))
+        c2 = walk(self.conv2, walk(self.combine1, torch.cat((walk(self.conv1, x), f4), dim=1)))
+        c4 = walk(self.conv4, walk(self.combine2, torch.cat((walk(self.conv3, c2), f5), dim=1)))
+        c6 = walk(self.conv6, walk(self.combine3, torch.cat((walk(self.conv5, c4), f6), dim=1)))
+        c7 = walk(self.conv7, c6, "mish", skip=walk(self.redir3, c4))
+        c8 = walk(self.conv8, c7, "mish", skip=walk(self.redir2, c2))
+        return walk(self.conv9, c8, "mish", skip=walk(self.redir1, x))
 
 
-class Hourglass(nn.Module):
+class Hourglass(net_blocks.Hourglass):
     """Parameters of the Mish hourglass (pwcnet_ddim.py:208-248): no bottleneck attention."""
 
     def __init__(self, c):
-        super().__init__()
-        self.conv1 = nn.Sequential(_cb3(c, 2 * c, 3, 2, 1), Mish())
-        self.conv2 = nn.Sequential(_cb3(2 * c, 2 * c, 3, 1, 1), Mish())
-        self.conv3 = nn.Sequential(_cb3(2 * c, 4 * c, 3, 2, 1), Mish())
-        self.conv4 = nn.Sequential(_cb3(4 * c, 4 * c, 3, 1, 1), Mish())
-        self.conv5 = nn.Sequential(nn.ConvTranspose3d(4 * c, 2 * c, 3, padding=1, output_padding=1, stride=2, bias=False),
-                                   nn.BatchNorm3d(2 * c))
-        self.conv6 = nn.Sequential(nn.ConvTranspose3d(2 * c, c, 3, padding=1, output_padding=1, stride=2, bias=False),
-                                   nn.BatchNorm3d(c))
-        self.redir1 = _cb3(c, c, 1, 1, 0)
-        self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
-
-    def forward(self, x):
-        """Training path (pwcnet_ddim.py:235-248); eval runs ``_HourglassPlan``."""
-        c2 = _train_seq(self.conv2, _train_seq(self.conv1, x))
-        c4 = _train_seq(self.conv4, _train_seq(self.conv3, c2))
-        c5 = _train_seq(self.conv5, c4, "mish", skip=_train_seq(self.redir2, c2))
-        return _train_seq(self.conv6, c5, "mish", skip=_train_seq(self.redir1, x))
+        super().__init__(c, "mish")
 
 
 # ---- prepared hot-path layers ---------------------------------------------------------------------
-def _deconv_plan(seq, act, redir=None):
-    """ConvTranspose3d + BN [+ the 1x1x1 `redir` conv + BN of the skip tensor folded into the same launch]."""
-    if redir is None:
-        return Deconv3dPlan(seq[0].weight, _bn_of(seq[1]), act=act, eps=seq[1].eps)
-    return Deconv3dPlan(seq[0].weight, _bn_of(seq[1]), act=act, eps=seq[1].eps,
-                        redir=(redir[0].weight, _bn_of(redir[1])), redir_eps=redir[1].eps)
+class _HourglassPlan(net_blocks.HourglassPlan):
+    """With the members of a step's first hourglass, whose input is filtered (``in_scale``)."""
 
-
-class _HourglassPlan:
     def __init__(self, hg: Hourglass):
-        self.conv1 = _plan_cb3(hg.conv1[0], 2, ACT_MISH)
-        self.conv2 = _plan_cb3(hg.conv2[0], 1, ACT_MISH)
-        self.conv3 = _plan_cb3(hg.conv3[0], 2, ACT_MISH)
-        self.conv4 = _plan_cb3(hg.conv4[0], 1, ACT_MISH)
-        self.conv5 = _deconv_plan(hg.conv5, ACT_MISH, hg.redir2)
-        self.conv6 = _deconv_plan(hg.conv6, ACT_MISH, hg.redir1)
-        self.conv6_plain = _deconv_plan(hg.conv6, ACT_MISH)        # filtered skip (first hourglass of a step)
-        self.redir1 = _plan_cb3(hg.redir1, 1, ACT_NONE)
-
-    def __call__(self, x, in_scale=None):
-        """``in_scale`` is the [0,1] volume filter: the reference feeds ``volume * noise`` to conv1 AND to
-        redir1 (pwcnet_ddim.py:472-474, :245), so both take the prologue."""
-        c1 = self.conv1(x, in_scale=in_scale)
-        c2 = self.conv2(c1)
-        c4 = self.conv4(self.conv3(c2))
-        c5 = self.conv5(c4, skip=c2)                                        # FMish(deconv + redir2)
-        if in_scale is None:
-            return self.conv6(c5, skip=x)                                   # FMish(deconv + redir1)
-        return self.conv6_plain(c5, residual=self.redir1(x, in_scale=in_scale))
+        super().__init__(hg, filtered=True)
 
 
 class _HourglassUpPlan:
@@ -368,15 +208,15 @@ class _HourglassUpPlan:
         self.conv1 = Conv3dPlan(m.conv1.weight, None, stride=2, act=ACT_NONE)
         self.conv3 = Conv3dPlan(m.conv3.weight, None, stride=2, act=ACT_NONE)
         self.conv5 = Conv3dPlan(m.conv5.weight, None, stride=2, act=ACT_NONE)
-        self.conv2 = _plan_cb3(m.conv2[0], 1, ACT_MISH)
-        self.conv4 = _plan_cb3(m.conv4[0], 1, ACT_MISH)
-        self.conv6 = _plan_cb3(m.conv6[0], 1, ACT_MISH)
-        self.combine1 = _plan_cb3(m.combine1[0], 1, ACT_MISH)
-        self.combine2 = _plan_cb3(m.combine2[0], 1, ACT_MISH)
-        self.combine3 = _plan_cb3(m.combine3[0], 1, ACT_MISH)
-        self.conv7 = _deconv_plan(m.conv7, ACT_MISH, m.redir3)
-        self.conv8 = _deconv_plan(m.conv8, ACT_MISH, m.redir2)
-        self.conv9 = _deconv_plan(m.conv9, ACT_MISH, m.redir1)
+        self.conv2 = plan_cb3(m.conv2[0], 1, ACT_MISH)
+        self.conv4 = plan_cb3(m.conv4[0], 1, ACT_MISH)
+        self.conv6 = plan_cb3(m.conv6[0], 1, ACT_MISH)
+        self.combine1 = plan_cb3(m.combine1[0], 1, ACT_MISH)
+        self.combine2 = plan_cb3(m.combine2[0], 1, ACT_MISH)
+        self.combine3 = plan_cb3(m.combine3[0], 1, ACT_MISH)
+        self.conv7 = deconv_plan(m.conv7, ACT_MISH, m.redir3)
+        self.conv8 = deconv_plan(m.conv8, ACT_MISH, m.redir2)
+        self.conv9 = deconv_plan(m.conv9, ACT_MISH, m.redir1)
 
     def __call__(self, x, f4, f5, f6):
         c1 = self.combine1(torch.cat((self.conv1(x), f4), dim=1))
@@ -388,25 +228,6 @@ class _HourglassUpPlan:
         c7 = self.conv7(c6, skip=c4)
         c8 = self.conv8(c7, skip=c2)
         return self.conv9(c8, skip=x)
-
-
-class _PairPlan:
-    def __init__(self, seq, act_last):
-        self.a = _plan_cb3(seq[0], 1, ACT_MISH)
-        last = seq[2]
-        self.b = _plan_cb3(last, 1, act_last) if isinstance(last, nn.Sequential) else \
-            Conv3dPlan(last.weight, None, stride=1, act=ACT_NONE)
-
-    def __call__(self, x, residual_self=False):
-        return self.b(self.a(x), residual=x if residual_self else None)
-
-
-def _plan_cb2(seq, act, dil=None):
-    """convbn 2-D (Conv2d + BatchNorm2d, submodule.py:21-24) -> fused plan.  ``dil``: the dilation LEFT of the layer's own
-    when its input is already de-interleaved into sub-images (`space_to_batch2`, level l: dil = dilation >> l)."""
-    conv, bn = seq[0], seq[1]
-    return Conv2dPlan(conv.weight, _bn_of(bn), dilation=conv.dilation[0] if dil is None else dil, act=act, eps=bn.eps,
-                      stride=conv.stride[0])
 
 
 def space_to_batch2(x: torch.Tensor) -> torch.Tensor:
@@ -424,21 +245,6 @@ def batch_to_space(x: torch.Tensor, levels: int) -> torch.Tensor:
     out = torch.empty((b, c, h << levels, w << levels), dtype=torch.float32, device=x.device)
     _lib.launch("dv_batch_to_space_f32", x.device, x.data_ptr(), out.data_ptr(), b, c, h << levels, w << levels, levels)
     return out
-
-
-class _Block2dPlan:
-    """BasicBlock (submodule.py:192-215): convbn+Mish, convbn, `out += x` (x through the 1x1 downsample when the
-    width changes); the add rides in the second convolution's epilogue, no activation after it."""
-
-    def __init__(self, blk: _Block2d, dil=None):
-        self.dilation = blk.conv2[0].dilation[0]
-        self.conv1 = _plan_cb2(blk.conv1[0], ACT_MISH, dil)
-        self.conv2 = _plan_cb2(blk.conv2, ACT_NONE, dil)
-        self.down = None if blk.downsample is None else _plan_cb2(blk.downsample, ACT_NONE)
-
-    def __call__(self, x, group=1):
-        skip = x if self.down is None else self.down(x)
-        return self.conv2(self.conv1(x, group=group), residual=skip, group=group)
 
 
 class _RefinePlan:
@@ -465,7 +271,7 @@ class _RefinePlan:
         """Layer i with `dil` of its dilation left to the kernel (the rest is in the tensor's de-interleave level)."""
         if (i, dil) not in self._cache:
             mod = self.mods[i]
-            plan = _plan_cb2(mod, ACT_MISH, dil) if isinstance(mod, nn.Sequential) else _Block2dPlan(mod, dil)
+            plan = plan_cb2(mod, ACT_MISH, dil) if isinstance(mod, nn.Sequential) else BasicBlockPlan(mod, dil)
             settle_build(self.conv8.wpacked.device)    # built on first use, after PlanCache.plans() returned: same guarantee
             self._cache[(i, dil)] = plan
         return self._cache[(i, dil)]
@@ -519,11 +325,11 @@ class _RefinePlan:
 
 class _Plans:
     def __init__(self, m: "PWCNet_ddim"):
-        self.dres0 = _PairPlan(m.dres0, ACT_MISH)
-        self.dres1 = _PairPlan(m.dres1, ACT_NONE)
+        self.dres0 = PairPlan(m.dres0)
+        self.dres1 = PairPlan(m.dres1)
         self.combine1 = _HourglassUpPlan(m.combine1)
         self.dres2, self.dres3, self.dres4 = (_HourglassPlan(h) for h in (m.dres2, m.dres3, m.dres4))
-        self.classif3 = _PairPlan(m.classif3, ACT_NONE)
+        self.classif3 = PairPlan(m.classif3)
         self.refinenet3 = _RefinePlan(m.refinenet3)
         conv, bn = m.dispupsample[0][0], m.dispupsample[0][1]          # 1x1 conv (1 -> 32) + BN folded to a*d + b
         g = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().float()
@@ -578,10 +384,8 @@ class _PWCCommon(PlanCache):
         with torch.no_grad(), torch.cuda.device(dev):
             return _Plans(self)
 
-    @torch.no_grad()
-    def fused_volume(self, fl, fr):
-        """pwcnet_ddim.py:608-641: four gwc(+concat) volumes -> dres0/dres1 -> hourglassup -> `combine`."""
-        p = self.prepare()
+    def _volumes(self, fl, fr):
+        """pwcnet_ddim.py:608-627: the four group-wise-correlation (+ concat) volumes at 1/4 .. 1/32."""
         vols = []
         for i, div in enumerate((4, 8, 16, 32), start=1):
             v = build_gwc_volume(fl[f"gw{i}"], fr[f"gw{i}"], self.maxdisp // div, self.num_groups)
@@ -590,6 +394,13 @@ class _PWCCommon(PlanCache):
                                          zero_left=True)
                 v = torch.cat((v, cv), 1)
             vols.append(v)
+        return vols
+
+    @torch.no_grad()
+    def fused_volume(self, fl, fr):
+        """pwcnet_ddim.py:608-641: four gwc(+concat) volumes -> dres0/dres1 -> hourglassup -> `combine`."""
+        p = self.prepare()
+        vols = self._volumes(fl, fr)
         cost0 = p.dres0(vols[0])
         cost0 = p.dres1(cost0, residual_self=True)
         return p.combine1(cost0, vols[1], vols[2], vols[3])
@@ -600,27 +411,17 @@ class _PWCCommon(PlanCache):
         self.concat_channels = 12 if use_concat_volume else 0
         self.feature_extraction = FeatureExtraction(use_concat_volume, 12)
         cin = self.num_groups + 2 * self.concat_channels
-        self.dres0 = nn.Sequential(_cb3(cin, 32, 3, 1, 1), Mish(), _cb3(32, 32, 3, 1, 1), Mish())
-        self.dres1 = nn.Sequential(_cb3(32, 32, 3, 1, 1), Mish(), _cb3(32, 32, 3, 1, 1))
+        self.dres0 = nn.Sequential(cb3(cin, 32, 3, 1, 1), Mish(), cb3(32, 32, 3, 1, 1), Mish())
+        self.dres1 = nn.Sequential(cb3(32, 32, 3, 1, 1), Mish(), cb3(32, 32, 3, 1, 1))
         self.combine1 = HourglassUp(32)
         if time_embedding:
             self.time_embedding = DynamicHead(d_model=48)
         self.dres2, self.dres3, self.dres4 = Hourglass(32), Hourglass(32), Hourglass(32)
         for i in range(5):
-            setattr(self, f"classif{i}", nn.Sequential(_cb3(32, 32, 3, 1, 1), Mish(), nn.Conv3d(32, 1, 3, 1, 1, bias=False)))
+            setattr(self, f"classif{i}", nn.Sequential(cb3(32, 32, 3, 1, 1), Mish(), nn.Conv3d(32, 1, 3, 1, 1, bias=False)))
         self.refinenet3 = RefineNet(146)
-        self.dispupsample = nn.Sequential(_cb2(1, 32, 1, 1, 0, 1), Mish())
-        for m in self.modules():
-            if isinstance(m, (nn.Conv2d, nn.Conv3d)) and not isinstance(m, nn.ConvTranspose3d):
-                n = m.out_channels
-                for k in m.kernel_size:
-                    n *= k
-                m.weight.data.normal_(0, math.sqrt(2.0 / n))
-            elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm3d)):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
-            elif isinstance(m, nn.Linear):
-                m.bias.data.zero_()
+        self.dispupsample = nn.Sequential(cb2(1, 32, 1, 1, 0, 1), Mish())
+        init_weights(self)
 
     @staticmethod
     def refine_features(features_left, features_right, size):
@@ -832,29 +633,15 @@ class PWCNet_ddim(train3d.TrainPrecision, _PWCCommon, nn.Module):
                                         "input gradient of the 3-D stack needs even dims at 1/4, 1/8 and 1/16")
         fl = self.feature_extraction(left)
         fr = self.feature_extraction(right)
-        vols = []
-        for i, div in enumerate((4, 8, 16, 32), start=1):
-            v = build_gwc_volume(fl[f"gw{i}"], fr[f"gw{i}"], self.maxdisp // div, self.num_groups)
-            if self.use_concat_volume:
-                cv = build_concat_volume(fl[f"concat_feature{i}"], fr[f"concat_feature{i}"], self.maxdisp // div,
-                                         zero_left=True)
-                v = torch.cat((v, cv), 1)
-            vols.append(v)
-        cost0 = _train_seq(self.dres0, vols[0])
-        cost0 = _train_seq(self.dres1, cost0) + cost0
+        vols = self._volumes(fl, fr)
+        cost0 = walk(self.dres0, vols[0])
+        cost0 = walk(self.dres1, cost0) + cost0
         combine = self.combine1(cost0, vols[1], vols[2], vols[3])
 
         # two-hot disp_volume_final (:644-659), then t, then q_sample's noise
         x_start = self.encode_disparity(disp.detach().float())
-        t = torch.randint(0, self.num_timesteps, (1,), device=x_start.device).long()
-        noise = torch.randn_like(x_start)
-        with torch.no_grad():                      # `torch.tensor(noisy)` (:667): no gradient reaches time_embedding
-            noisy = (self.sqrt_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * x_start
-                     + self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(-1, 1, 1, 1) * noise)
-            noisy = self.time_embedding(noisy, t)
-            noisy = torch.clamp(noisy, min=-1 * self.scale, max=self.scale)
-            noisy = ((noisy / self.scale) + 1) / 2.
-            noisy = noisy.unsqueeze(1).to(torch.float32)
+        noisy = ddim.train_filter(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.time_embedding,
+                                  self.scale, self.num_timesteps, x_start)
 
         out1 = self.dres2(combine * noisy)
         out2 = self.dres3(out1)
@@ -862,11 +649,11 @@ class PWCNet_ddim(train3d.TrainPrecision, _PWCCommon, nn.Module):
         size = [self.maxdisp, hh, ww]
 
         # the fused tail with its HIP backward (train_tail.py; DV_TRAIN_TAIL)
-        pred0 = regress_head(_train_seq(self.classif0, cost0), size, align_corners=True)
-        pred1 = regress_head(_train_seq(self.classif1, out1), size, align_corners=True)
-        pred2 = regress_head(_train_seq(self.classif2, out2), size, align_corners=True)
-        pred3 = regress_head(_train_seq(self.classif3, out3), size, align_corners=True).unsqueeze(1)
-        pred_combine = regress_head(_train_seq(self.classif4, combine), size, align_corners=True)
+        pred0 = regress_head(walk(self.classif0, cost0), size, align_corners=True)
+        pred1 = regress_head(walk(self.classif1, out1), size, align_corners=True)
+        pred2 = regress_head(walk(self.classif2, out2), size, align_corners=True)
+        pred3 = regress_head(walk(self.classif3, out3), size, align_corners=True).unsqueeze(1)
+        pred_combine = regress_head(walk(self.classif4, combine), size, align_corners=True)
 
         # refinement (:711-728)
         # (:487-492 on the route of train_net2d: DV_TRAIN_NET2D=hip resizes on the HIP kernel with the atomics-free backward)
@@ -900,7 +687,7 @@ class PWCNet_ddim(train3d.TrainPrecision, _PWCCommon, nn.Module):
             n = x.numel() // x.shape[1]
             bn.running_mean.mul_(1 - factor).add_((factor * mean.reshape(-1)).float())
             bn.running_var.mul_(1 - factor).add_((factor * var.reshape(-1) * n / max(n - 1, 1)).float())
-        return fmish(y).float()
+        return act_statement(y, "mish").float()
 
     def forward(self, left, right, used, disp, mask=None):
         if self.training:

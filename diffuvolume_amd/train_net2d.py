@@ -16,7 +16,9 @@ ATen's atomic backward of ``F.interpolate``), ``hip`` runs
     rewrites its buffers on every call): packed once per optimizer step, shared by the left and the right image.
     A BatchNorm2d in training mode with running statistics and affine parameters is ``train_norm.batch_norm_act_train``
     (``relu`` / ``mish`` / ``none``, the BasicBlock's residual as ``skip``; csrc/bn3d_act.hip takes [B,C,S] for any S)
-    behind the module's own ``num_batches_tracked`` bump; any other BatchNorm keeps the PyTorch statement.
+    behind the module's own ``num_batches_tracked`` bump; any other BatchNorm keeps the PyTorch statement.  Which leaf of
+    a Sequential rides in which statement is decided by ``net_blocks.walk``; ``bn_act2d`` shares its body with
+    ``train_norm.bn_act`` (``bn_act_rank``) and the PyTorch statement is ``train_norm.act_statement``.
 
 All reductions behind these are partials combined in a fixed order: the same bits on every launch.  CPU tensors raise,
 as everywhere on the hot path."""
@@ -32,7 +34,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _env, _lib, train2d
 from .submodule import ACT_NONE, weight_key
-from .train_norm import ACTS, batch_norm_act_train
+from .net_blocks import walk
+from .train_norm import bn_act_rank
 
 SLOT = "net2d"
 
@@ -109,52 +112,29 @@ def build_plans(owner: nn.Module, prefixes=None):
         return _key(convs), [train2d.TrainConvPlan(m, ACT_NONE) for m in convs]
 
 
-def _is_mish(m: nn.Module) -> bool:
-    return type(m).__name__ == "Mish"
-
-
-def _leaves(m: nn.Module):
-    if isinstance(m, nn.Sequential):
-        for c in m:
-            yield from _leaves(c)
-    else:
-        yield m
-
-
-def _act(y: torch.Tensor, act: str) -> torch.Tensor:
-    if act == "relu":
-        return F.relu(y)
-    if act == "mish":
-        return y * torch.tanh(F.softplus(y))
-    if act != "none":
-        raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
-    return y
-
-
 def bn_act2d(bn: nn.Module, x: torch.Tensor, act: str, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """act(bn(x) + skip) for a BatchNorm2d of a training graph on the HIP route: inside the kernel's case -- module in
-    training mode with running statistics, a momentum and affine parameters, x a contiguous float32 4-D tensor --
-    ``batch_norm_act_train`` after the module's own ``num_batches_tracked`` bump; outside it the module's forward and the
-    PyTorch statement."""
-    inside = (bn.training and bn.track_running_stats and bn.momentum is not None and bn.weight is not None
-              and bn.bias is not None and bn.running_mean is not None and x.dim() == 4 and x.dtype == torch.float32
-              and x.is_contiguous() and (skip is None or (skip.dtype == torch.float32 and skip.is_contiguous())))
-    if not inside:
-        y = bn(x)
-        return _act(y if skip is None else y + skip, act)
-    y = batch_norm_act_train(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum, eps=bn.eps,
-                             act=act, skip=skip)
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    return y
+    """act(bn(x) + skip) for a BatchNorm2d of a training graph on the HIP route: ``train_norm.bn_act_rank`` for 4-D tensors
+    -- inside the kernel's case ``batch_norm_act_train`` after the module's own ``num_batches_tracked`` bump; outside it
+    the module's forward and the PyTorch statement."""
+    return bn_act_rank(4, bn, x, act, skip)
 
 
 class Net2d:
-    """The HIP route of the 2-D statements of one ``owner`` (a ``PlanCache`` module whose ``_build_plans("net2d")`` is
-    ``build_plans``) for one call: resolves the slot once -- rebuilt when a convolution weight was written or swapped --
-    and then runs convolutions, Sequentials and BasicBlocks below the owner."""
+    """The 2-D statements of a training graph for one call: convolutions, Sequentials and BasicBlocks.
 
-    def __init__(self, owner: nn.Module, prefixes=None):
+    ``Net2d(owner[, prefixes])`` is the HIP route below one ``owner`` (a ``PlanCache`` module whose
+    ``_build_plans("net2d")`` is ``build_plans``): it resolves the slot once -- rebuilt when a convolution weight was
+    written or swapped -- and sends every BatchNorm2d to ``bn_act2d``.  ``Net2d(conv2d=fn)`` has no packed plans (PCW's
+    refinenet3): every Conv2d runs on ``fn``, a BatchNorm2d on ``bn_act2d`` only where ``route()`` is ``hip`` and on its own
+    forward otherwise."""
+
+    def __init__(self, owner: Optional[nn.Module] = None, prefixes=None, conv2d=None):
+        if (owner is None) == (conv2d is None):
+            raise ValueError("Net2d takes an owner with packed plans or a conv2d function")
+        self.conv2d, self.plan = conv2d, {}
+        self.bn2d = bn_act2d if owner is not None or route() == "hip" else None
+        if owner is None:
+            return
         convs = _convs(owner, prefixes)
         key = _key(convs)
         if owner.plans(SLOT)[0] != key:
@@ -165,6 +145,8 @@ class Net2d:
         self.plan = {id(m): p for m, p in zip(convs, plans)}
 
     def conv(self, m: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+        if self.conv2d is not None:
+            return self.conv2d(m, x)
         _lib.check_f32(x, "x")
         p = self.plan.get(id(m))
         if p is None:
@@ -172,31 +154,9 @@ class Net2d:
         return train2d.ConvCatFn.apply(p, m.weight, m.bias, x)
 
     def seq(self, mod: nn.Module, x: torch.Tensor, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``mod(x) + skip`` for a (nested) Sequential of Conv2d, BatchNorm2d, ReLU and Mish.  A BatchNorm2d takes the
-        activation behind it, or -- when it ends the walk -- the skip, into its kernel."""
-        mods = list(_leaves(mod))
-        i, n = 0, len(mods)
-        while i < n:
-            m = mods[i]
-            step = 1
-            if isinstance(m, nn.Conv2d):
-                x = self.conv(m, x)
-            elif isinstance(m, nn.BatchNorm2d):
-                act = "none"
-                if i + 1 < n and isinstance(mods[i + 1], nn.ReLU):
-                    act, step = "relu", 2
-                elif i + 1 < n and _is_mish(mods[i + 1]):
-                    act, step = "mish", 2
-                s = skip if (i + 1 == n) else None
-                x = bn_act2d(m, x, act, s)
-                if s is not None:
-                    skip = None
-            elif isinstance(m, nn.ReLU):
-                x = F.relu(x)
-            else:
-                x = m(x)
-            i += step
-        return x if skip is None else x + skip
+        """``mod(x) + skip`` for a (nested) Sequential of Conv2d, BatchNorm2d, ReLU and Mish (``net_blocks.walk``): a
+        BatchNorm2d takes the activation behind it, or -- when it ends the walk -- the skip, into its kernel."""
+        return walk(mod, x, "none", skip, conv2d=self.conv, bn2d=self.bn2d)
 
     def block(self, blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
         """A BasicBlock: conv2(conv1(x)) + (x, or downsample(x))."""

@@ -16,7 +16,9 @@ There is no double backward.  ``DV_TRAIN_NORM=torch`` routes the function to the
 CPU tensors raise, as everywhere on the hot path.
 
 ``bn_act(bn, x, act, skip=None)`` is the call site's form: it takes the ``nn.BatchNorm3d`` module, bumps
-``num_batches_tracked`` and keeps the PyTorch statement for whatever lies outside the kernel's case."""
+``num_batches_tracked`` and keeps the PyTorch statement for whatever lies outside the kernel's case.  Its body,
+``bn_act_rank``, also serves ``train_net2d.bn_act2d`` (rank 4), and ``act_statement(y, act, skip=None)`` is the one PyTorch
+spelling of ``act(y + skip)`` for the whole package (``net_blocks.walk`` ends every Sequential with it)."""
 from __future__ import annotations
 
 import functools
@@ -34,15 +36,17 @@ ACTS = {"none": 0, "relu": 1, "mish": 2}            # DV_ACT_NONE / DV_ACT_RELU 
 route = functools.partial(_env.route, "DV_TRAIN_NORM")
 
 
-def _statement(x, weight, bias, running_mean, running_var, momentum, eps, act, skip):
-    """The PyTorch statement as the call sites ran it before the kernels."""
-    y = F.batch_norm(x, running_mean, running_var, weight, bias, True, momentum, eps)
+def act_statement(y: torch.Tensor, act: str, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(y + skip) in PyTorch: ``"relu"``, ``"mish"`` (x * tanh(softplus(x)), KITTI12/models/submodule.py:11-18) or
+    ``"none"``."""
     if skip is not None:
         y = y + skip
     if act == "relu":
         return F.relu(y)
     if act == "mish":
         return y * torch.tanh(F.softplus(y))
+    if act != "none":
+        raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
     return y
 
 
@@ -121,34 +125,31 @@ def batch_norm_act_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tens
     if x.numel() <= c:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
     if r == "torch":
-        return _statement(x, weight, bias, running_mean, running_var, momentum, eps, act, skip)
+        # the PyTorch statement as the call sites ran it before the kernels
+        return act_statement(F.batch_norm(x, running_mean, running_var, weight, bias, True, momentum, eps), act, skip)
     for name in ("running_mean", "running_var"):
         if named[name] is not None and not named[name].is_contiguous():
             raise RuntimeError(f"{name} must be contiguous (it is updated in place)")
     return BatchNormActFn.apply(x, weight, bias, running_mean, running_var, skip, float(momentum), float(eps), ACTS[act])
 
 
-def bn_act(bn: torch.nn.Module, x: torch.Tensor, act: str, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """act(bn(x) + skip) for a BatchNorm3d module of a training graph.  Inside the kernel's case -- module in training mode
-    with running statistics, a momentum and affine parameters, x a contiguous float32 5-D tensor -- this is
-    ``batch_norm_act_train`` (on the route of DV_TRAIN_NORM) after the module's own ``num_batches_tracked`` bump; outside
-    it, the module's forward and the PyTorch statement on either route."""
+def bn_act_rank(rank: int, bn: torch.nn.Module, x: torch.Tensor, act: str, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(bn(x) + skip) for a BatchNorm module of a training graph.  Inside the kernel's case -- module in training mode
+    with running statistics, a momentum and affine parameters, x a contiguous float32 tensor of ``rank`` dimensions -- this
+    is ``batch_norm_act_train`` (on the route of DV_TRAIN_NORM) after the module's own ``num_batches_tracked`` bump;
+    outside it, the module's forward and the PyTorch statement on either route."""
     inside = (bn.training and bn.track_running_stats and bn.momentum is not None and bn.weight is not None
-              and bn.bias is not None and bn.running_mean is not None and x.dim() == 5 and x.dtype == torch.float32
+              and bn.bias is not None and bn.running_mean is not None and x.dim() == rank and x.dtype == torch.float32
               and x.is_contiguous() and (skip is None or (skip.dtype == torch.float32 and skip.is_contiguous())))
     if not inside:
-        y = bn(x)
-        if skip is not None:
-            y = y + skip
-        if act == "relu":
-            return F.relu(y)
-        if act == "mish":
-            return y * torch.tanh(F.softplus(y))
-        if act != "none":
-            raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
-        return y
+        return act_statement(bn(x), act, skip)
     y = batch_norm_act_train(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum, eps=bn.eps,
                              act=act, skip=skip)
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return y
+
+
+def bn_act(bn: torch.nn.Module, x: torch.Tensor, act: str, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 3-D stacks' call site: an nn.BatchNorm3d on [B,C,D,H,W] (a 4-D tensor goes to the module's forward)."""
+    return bn_act_rank(5, bn, x, act, skip)
