@@ -1,5 +1,6 @@
 """ctypes binding of libdiffuvolume_hip.so (the C ABI in include/diffuvolume_hip.h, include/diffuvolume_hip_train.h,
-include/diffuvolume_hip_volume_train.h and include/diffuvolume_hip_amp3d.h).
+include/diffuvolume_hip_volume_train.h, include/diffuvolume_hip_amp3d.h, include/diffuvolume_hip_amp3d_bf16.h and
+include/diffuvolume_hip_amp2d_bf16.h).
 
 There is deliberately no CPU / eager fallback: if the library is missing or a
 kernel reports an error the call raises.  ``import torch`` happens first so the
@@ -247,6 +248,34 @@ AMP3D_BF16_SIGNATURES = {
 }
 
 
+# Sixth table: include/diffuvolume_hip_amp2d_bf16.h, IGEV's update block at train precision "bf16": the bf16 twins of the
+# fp16 entries of SIGNATURES (dv_conv2d_f16_*, dv_conv2d_1in_f16, dv_gru_*_f16, dv_conv2d_wgrad_cat_f16*), each with its
+# twin's signature.  The sizes and the K-split choice are the fp16 entries' (dv_conv2d_f16_packed_bytes,
+# dv_conv2d_f16_auto_kslices): they do not depend on the element type.  tests/test_update_bf16_host.py reads this table.
+PACKS_WEIGHTS = "packs weights: writes the packed image only, held with the plan by the forward tests"
+_HELD2D = "test_gpu_update_bf16_abi.py::"
+AMP2D_BF16_SIGNATURES = {
+    "dv_conv2d_bf16_pack_weights": (c_int, [P, P, I, I, I, P], PACKS_WEIGHTS),
+    "dv_conv2d_bf16_cat": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+                           held_by(_HELD2D + "test_conv2d_bf16_cat_abi_offset_views_bounds_and_refusals")),
+    "dv_conv2d_bf16_cat_ksplit": (c_int, [P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+                                  held_by(_HELD2D + "test_conv2d_bf16_cat_abi_offset_views_bounds_and_refusals")),
+    "dv_conv2d_bf16_cat_pair": (c_int, [P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+                                held_by(_HELD2D + "test_conv2d_bf16_pair_abi_offset_views_bounds_and_refusals")),
+    "dv_conv2d_bf16_cat_pair_ksplit": (c_int, [P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+                                       held_by(_HELD2D + "test_conv2d_bf16_pair_abi_offset_views_bounds_and_refusals")),
+    "dv_conv2d_1in_bf16": (c_int, [P, P, P, P, I, I, I, I, I, I, P],
+                           held_by(_HELD2D + "test_conv2d_1in_bf16_abi_offset_views_bounds_and_refusals")),
+    "dv_gru_reset_mul_bf16": (c_int, [P, P, P, c_size_t, P],
+                              held_by(_HELD2D + "test_gru_gates_bf16_abi_offset_views_bounds_and_refusals")),
+    "dv_gru_blend_bf16": (c_int, [P, P, P, P, c_size_t, P],
+                          held_by(_HELD2D + "test_gru_gates_bf16_abi_offset_views_bounds_and_refusals")),
+    "dv_conv2d_wgrad_cat_bf16_workspace_floats": (c_size_t, [P, I, I, I, I, I, I], SIZE_ONLY),
+    "dv_conv2d_wgrad_cat_bf16": (c_int, [P, P, I, P, P, P, I, I, I, I, I, P],
+                                 held_by(_HELD2D + "test_conv2d_wgrad_cat_bf16_abi_offset_views_bounds_and_refusals")),
+}
+
+
 class DiffuVolumeError(RuntimeError):
     pass
 
@@ -266,7 +295,8 @@ def load() -> ctypes.CDLL:
             "(there is no CPU fallback for the DiffuVolume hot path)")
     lib = ctypes.CDLL(os.fspath(_LIB_PATH), mode=ctypes.RTLD_GLOBAL)
     tables = {**SIGNATURES, **TRAIN_SIGNATURES, **{k: v[:2] for k, v in VOLUME_TRAIN_SIGNATURES.items()},
-              **{k: v[:2] for k, v in AMP3D_SIGNATURES.items()}, **{k: v[:2] for k, v in AMP3D_BF16_SIGNATURES.items()}}
+              **{k: v[:2] for k, v in AMP3D_SIGNATURES.items()}, **{k: v[:2] for k, v in AMP3D_BF16_SIGNATURES.items()},
+              **{k: v[:2] for k, v in AMP2D_BF16_SIGNATURES.items()}}
     for name, (res, args) in tables.items():
         fn = getattr(lib, name)          # AttributeError => ABI mismatch, also loud
         fn.restype = res

@@ -1,59 +1,52 @@
-// K13 at fp16: the 2-D convolutions of IGEV's update block under fp16 autocast (`mixed_precision=True`,
-// KITTI15/core/update.py:26-142 run inside `autocast(enabled=self.args.mixed_precision)`, igev_stereo_ddim.py:242-246) on
-// v_mfma_f32_16x16x32_f16.  The rounding contract, the GEMM view, the LDS layout, the pair launch and the K-split are
-// csrc/conv2d_mp.h's, written once for fp16 and bf16; this file is the fp16 instantiation (its kernels and its entries)
-// and the two entries that serve both element types: the size of the packed image and the K-split choice.
+// K13 at bf16: the 2-D convolutions of IGEV's update block at train precision "bf16" (KITTI15/core/update.py:26-142,
+// the training loop of train_stereo.py:146-173 under `torch.autocast("cuda", dtype=torch.bfloat16)`) on
+// v_mfma_f32_16x16x32_bf16: operands, the convolution result and every epilogue result rounded by rb16 (round to nearest
+// even bfloat16 by v_cvt_pk_bf16_f32; NaN stays NaN, a finite float32 above about 3.3895e38 rounds to Inf, operands below
+// 2^-126 may be flushed to zero).  Everything else is csrc/conv2d_mp.h's, written once for fp16 and bf16; this file is the
+// bf16 instantiation and its entries.  The packed image has dv_conv2d_f16_packed_bytes bytes and the K-split choice is
+// dv_conv2d_f16_auto_kslices: neither depends on the element type.
 #include "conv2d_mp.h"
 
 namespace {
 
 template <int KS, int NT>
-__global__ __launch_bounds__(256, 2) void conv2d_f16_kernel(MpConvArgs a) {
-  conv2d_mp_body<MpF16, KS, NT>(a);
+__global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(MpConvArgs a) {
+  conv2d_mp_body<MpBf16, KS, NT>(a);
 }
 
-__global__ __launch_bounds__(256) void conv2d_f16_ksplit_epilogue_kernel(MpConvArgs a) {
-  conv2d_mp_ksplit_epilogue_body<MpF16>(a);
+__global__ __launch_bounds__(256) void conv2d_bf16_ksplit_epilogue_kernel(MpConvArgs a) {
+  conv2d_mp_ksplit_epilogue_body<MpBf16>(a);
 }
 
-__global__ void pack_f16_kernel(const float* __restrict__ w, MpF16::elem* __restrict__ wpk, int Cin, int Cout, int kk,
-                                int n16, size_t total) {
-  conv2d_mp_pack_body<MpF16>(w, wpk, Cin, Cout, kk, n16, total);
+__global__ void pack_bf16_kernel(const float* __restrict__ w, MpBf16::elem* __restrict__ wpk, int Cin, int Cout, int kk,
+                                 int n16, size_t total) {
+  conv2d_mp_pack_body<MpBf16>(w, wpk, Cin, Cout, kk, n16, total);
 }
 
 struct Kernels {
   template <int KS, int NT>
   static void conv(dim3 grid, hipStream_t s, const MpConvArgs& a) {
-    hipLaunchKernelGGL((conv2d_f16_kernel<KS, NT>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((conv2d_bf16_kernel<KS, NT>), grid, dim3(256), 0, s, a);
   }
   static void ksplit_epilogue(dim3 grid, hipStream_t s, const MpConvArgs& a) {
-    hipLaunchKernelGGL(conv2d_f16_ksplit_epilogue_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(conv2d_bf16_ksplit_epilogue_kernel, grid, dim3(256), 0, s, a);
   }
   static void pack(dim3 grid, hipStream_t s, const float* w, void* wpacked, int Cin, int Cout, int kk, int n16,
                    size_t total) {
-    hipLaunchKernelGGL(pack_f16_kernel, grid, dim3(256), 0, s, w, static_cast<MpF16::elem*>(wpacked), Cin, Cout, kk, n16,
+    hipLaunchKernelGGL(pack_bf16_kernel, grid, dim3(256), 0, s, w, static_cast<MpBf16::elem*>(wpacked), Cin, Cout, kk, n16,
                        total);
   }
 };
 
 }  // namespace
 
-// (16-bit elements of either type: dv_conv2d_bf16_pack_weights fills an image of the same size)
-extern "C" size_t dv_conv2d_f16_packed_bytes(int Cin, int Cout, int k) {
-  return conv2d_mp_packed_elems(Cin, Cout, k) * sizeof(MpF16::elem);
-}
+#include "../../include/diffuvolume_hip_amp2d_bf16.h"
 
-// (the launch geometry does not depend on the element type: the bf16 entries take the same choice)
-extern "C" int dv_conv2d_f16_auto_kslices(int Cin, int H, int W, int Cout, int k) {
-  if (Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 1;
-  return auto_kslices(Cin, H, W, Cout, k);
-}
-
-extern "C" int dv_conv2d_f16_pack_weights(const float* w, void* wpacked, int Cin, int Cout, int k, dv_stream_t stream) {
+extern "C" int dv_conv2d_bf16_pack_weights(const float* w, void* wpacked, int Cin, int Cout, int k, dv_stream_t stream) {
   return conv2d_mp_pack<Kernels>(w, wpacked, Cin, Cout, k, stream);
 }
 
-extern "C" int dv_conv2d_f16_cat(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+extern "C" int dv_conv2d_bf16_cat(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
                                  const float* bias, const float* residual, const float* mul, const float* blend_z,
                                  const float* blend_h, float* out, int B, int H, int W, int Cout, int k, int act,
                                  dv_stream_t stream) {
@@ -61,7 +54,7 @@ extern "C" int dv_conv2d_f16_cat(const float* const* inputs, const int* channels
                                 1, B, H, W, Cout, k, act, stream);
 }
 
-extern "C" int dv_conv2d_f16_cat_ksplit(const float* const* inputs, const int* channels, int n_inputs,
+extern "C" int dv_conv2d_bf16_cat_ksplit(const float* const* inputs, const int* channels, int n_inputs,
                                         const void* wpacked, const float* bias, const float* residual, const float* mul,
                                         const float* blend_z, const float* blend_h, float* out, float* scratch,
                                         int kslices, int B, int H, int W, int Cout, int k, int act, dv_stream_t stream) {
@@ -69,7 +62,7 @@ extern "C" int dv_conv2d_f16_cat_ksplit(const float* const* inputs, const int* c
                                 kslices, B, H, W, Cout, k, act, stream);
 }
 
-extern "C" int dv_conv2d_f16_cat_pair(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
+extern "C" int dv_conv2d_bf16_cat_pair(const float* const* inputs, const int* channels, int n_inputs, const void* wpacked,
                                       const float* bias, const float* residual1, const float* mul1, float* out1,
                                       const float* residual2, const float* mul2, float* out2, int B, int H, int W,
                                       int Cout1, int Cout2, int act, dv_stream_t stream) {
@@ -77,7 +70,7 @@ extern "C" int dv_conv2d_f16_cat_pair(const float* const* inputs, const int* cha
                                      out2, nullptr, 1, B, H, W, Cout1, Cout2, act, stream);
 }
 
-extern "C" int dv_conv2d_f16_cat_pair_ksplit(const float* const* inputs, const int* channels, int n_inputs,
+extern "C" int dv_conv2d_bf16_cat_pair_ksplit(const float* const* inputs, const int* channels, int n_inputs,
                                              const void* wpacked, const float* bias, const float* residual1,
                                              const float* mul1, float* out1, const float* residual2, const float* mul2,
                                              float* out2, float* scratch, int kslices, int B, int H, int W, int Cout1,

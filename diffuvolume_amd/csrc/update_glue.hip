@@ -3,20 +3,30 @@
 // call at batch 4) and a naive MIOpen solver for the single-input-channel 7x7 (0.7 ms): 23 % of an iteration.
 //   dv_conv2d_1in_f32         nn.Conv2d(1, Cout, K, padding=K/2) + bias + activation   (BasicMotionEncoder.convd1, :86,:92)
 //   dv_conv2d_1in_f16         the same under fp16 autocast (operands and output rounded to fp16, fp32 accumulation)
+//   dv_conv2d_1in_bf16        the same at train precision "bf16" (the other rounding function of csrc/mp_elem.h)
 //   dv_resize_bilinear_ac_f32 F.interpolate(x, size, mode='bilinear', align_corners=True)   (`interp`, update.py:100-102)
 //   dv_avg_pool3s2_f32        F.avg_pool2d(x, 3, stride=2, padding=1)  (count_include_pad)    (`pool2x`, update.py:96-97)
-#include "dv_common.h"
+#include "mp_elem.h"
+#include "../../include/diffuvolume_hip_amp2d_bf16.h"
 
 namespace {
 
 // ---- one input channel, K x K taps (K odd <= 7), Cout channels: VALU.  Block = 16 x 16 pixels; the haloed input
 // tile and the whole weight set sit in LDS; a thread keeps its K*K window in registers and walks the output channels
-// with broadcast reads of the weights (every lane reads the same address).  R16: the fp16-autocast form (`convd1` under
-// `mixed_precision`): input, weights and bias rounded to fp16 as they are staged, fp32 accumulation, the output rounded
-// to fp16 before the activation ----
-__device__ __forceinline__ float r16_1in(float v) { return (float)(_Float16)v; }
+// with broadcast reads of the weights (every lane reads the same address).  R: the rounding of the 16-bit forms (`convd1`
+// under `mixed_precision` / at train precision "bf16"): input, weights and bias rounded as they are staged, fp32
+// accumulation, the output rounded before the activation; Round1inNone is the fp32 form ----
+struct Round1inNone {
+  static constexpr bool ON = false;
+  static __device__ __forceinline__ float r(float v) { return v; }
+};
+template <class T>
+struct Round1in {                                  // T: MpF16 (r16) or MpBf16 (rb16)
+  static constexpr bool ON = true;
+  static __device__ __forceinline__ float r(float v) { return (float)T::round(v); }
+};
 
-template <int K, bool R16 = false>
+template <int K, class R = Round1inNone>
 __global__ __launch_bounds__(256) void conv2d_1in_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                          const float* __restrict__ bias, float* __restrict__ out,
                                                          int H, int W, int Cout, int act, int ntx, int nty) {
@@ -35,9 +45,9 @@ __global__ __launch_bounds__(256) void conv2d_1in_kernel(const float* __restrict
     const int yy = i / IT, xx = i - yy * IT;
     const int y = y0 - P + yy, x = x0 - P + xx;
     const float v = ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? ib[(size_t)y * W + x] : 0.f;
-    in_s[i] = R16 ? r16_1in(v) : v;
+    in_s[i] = R::r(v);
   }
-  for (int i = tid; i < Cout * K * K; i += 256) w_s[i] = R16 ? r16_1in(w[i]) : w[i];
+  for (int i = tid; i < Cout * K * K; i += 256) w_s[i] = R::r(w[i]);
   __syncthreads();
   const int ly = tid >> 4, lx = tid & 15;
   float win[K * K];
@@ -50,12 +60,12 @@ __global__ __launch_bounds__(256) void conv2d_1in_kernel(const float* __restrict
   float* ob = out + ((size_t)b * Cout * H + y) * W + x;
   for (int co = 0; co < Cout; ++co) {
     const float* wc = w_s + co * K * K;
-    float acc = bias ? (R16 ? r16_1in(bias[co]) : bias[co]) : 0.f;
+    float acc = bias ? R::r(bias[co]) : 0.f;
 #pragma unroll
     for (int i = 0; i < K * K; ++i) acc = fmaf(win[i], wc[i], acc);
-    if (R16) {
-      const float v = dv_act(r16_1in(acc), act);
-      ob[(size_t)co * H * W] = act == DV_ACT_RELU || act == DV_ACT_NONE ? v : r16_1in(v);
+    if (R::ON) {
+      const float v = dv_act(R::r(acc), act);
+      ob[(size_t)co * H * W] = act == DV_ACT_RELU || act == DV_ACT_NONE ? v : R::r(v);
     } else {
       ob[(size_t)co * H * W] = dv_act(acc, act);
     }
@@ -129,7 +139,7 @@ __global__ void avg_pool3s2_kernel(const float* __restrict__ in, float* __restri
 
 }  // namespace
 
-template <bool R16>
+template <class R>
 static int conv2d_1in_run(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int Cout, int k,
                    int act, dv_stream_t stream) {
   DV_REQUIRE_PTR(in);
@@ -146,20 +156,25 @@ static int conv2d_1in_run(const float* in, const float* w, const float* bias, fl
   DV_REQUIRE(blocks <= 0x7fffffffLL, DV_ERR_SHAPE);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks), block(256);
-  if (k == 3) hipLaunchKernelGGL((conv2d_1in_kernel<3, R16>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
-  else if (k == 5) hipLaunchKernelGGL((conv2d_1in_kernel<5, R16>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
-  else hipLaunchKernelGGL((conv2d_1in_kernel<7, R16>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
+  if (k == 3) hipLaunchKernelGGL((conv2d_1in_kernel<3, R>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
+  else if (k == 5) hipLaunchKernelGGL((conv2d_1in_kernel<5, R>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
+  else hipLaunchKernelGGL((conv2d_1in_kernel<7, R>), grid, block, lds, s, in, w, bias, out, H, W, Cout, act, ntx, nty);
   return dv_launch_status();
 }
 
 extern "C" int dv_conv2d_1in_f32(const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
                                  int Cout, int k, int act, dv_stream_t stream) {
-  return conv2d_1in_run<false>(in, w, bias, out, B, H, W, Cout, k, act, stream);
+  return conv2d_1in_run<Round1inNone>(in, w, bias, out, B, H, W, Cout, k, act, stream);
 }
 
 extern "C" int dv_conv2d_1in_f16(const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
                                  int Cout, int k, int act, dv_stream_t stream) {
-  return conv2d_1in_run<true>(in, w, bias, out, B, H, W, Cout, k, act, stream);
+  return conv2d_1in_run<Round1in<MpF16>>(in, w, bias, out, B, H, W, Cout, k, act, stream);
+}
+
+extern "C" int dv_conv2d_1in_bf16(const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
+                                  int Cout, int k, int act, dv_stream_t stream) {
+  return conv2d_1in_run<Round1in<MpBf16>>(in, w, bias, out, B, H, W, Cout, k, act, stream);
 }
 
 extern "C" int dv_resize_bilinear_ac_f32(const float* in, float* out, int BC, int h, int w, int H, int W,

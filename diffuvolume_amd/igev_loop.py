@@ -54,6 +54,13 @@ def round_gru_inputs_f16(net_list, inp_list):
     return [r(t) for t in net_list], [[r(t) for t in trio] for trio in inp_list]
 
 
+def round_gru_inputs_bf16(net_list, inp_list):
+    """The bf16 twin of ``round_gru_inputs_f16`` for ``forward_train(amp=torch.bfloat16)``: values rounded to bfloat16 (kept
+    as float32), and through the same casts their gradients."""
+    r = lambda t: t.bfloat16().float() if isinstance(t, torch.Tensor) else t
+    return [r(t) for t in net_list], [[r(t) for t in trio] for trio in inp_list]
+
+
 class IGEVDiffusionLoop:
     def __init__(self, time_embedding: DynamicHead180, update_block: Callable, upsample_disp: Callable,
                  n_gru_layers: int = 3, slow_fast_gru: bool = False, sampling_timesteps: int = 2,

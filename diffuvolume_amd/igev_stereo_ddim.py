@@ -21,7 +21,7 @@ from . import _lib, ddim
 from .igev_front2d import Feature, MultiBasicEncoder, _front2d
 from .igev_layers import (HIP, TRAIN, BasicConv, BasicConv_IN, Conv2x, Conv2x_IN, _Conv2xBase, _FewInPlan,  # noqa: F401
                           _PLAN_CACHE, _bn_tuple, _require_cuda, _stem, _train_mode, _wants_autograd, freeze_bn)
-from .igev_loop import DynamicHead180, IGEVDiffusionLoop, round_gru_inputs_f16
+from .igev_loop import DynamicHead180, IGEVDiffusionLoop, round_gru_inputs_bf16, round_gru_inputs_f16
 from .igev_upsample import (_context_upsample_launch, _context_upsample_shapes, _spx_init_train, _spx_plans,  # noqa: F401
                             _spx_train_key, _spx_train_plans, _upsample_disp, _upsample_disp_train, context_upsample)
 from .igev_volume import (FeatureAtt, _cost_volume, _cost_volume_plans, _cost_volume_train, _run, _run_train,  # noqa: F401
@@ -186,7 +186,15 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
         lookup and the upsampling head stay float32 (a deliberate difference: the reference autocasts them too), and all
         outputs are float32.  Step through ``torch.amp.GradScaler``: a scaled loss that overflows fp16 inside the block
         gives Inf / NaN gradients and the scaler skips the step.  The call takes no ``torch.autocast`` of the caller's
-        and ``args.mixed_precision=True`` alone does not select it: both raise and point here."""
+        and ``args.mixed_precision=True`` alone does not select it: both raise and point here.
+
+        ``amp`` takes ``False``, ``True``, ``torch.float16`` (the same as ``True``) and ``torch.bfloat16``; anything else
+        raises ValueError.  ``amp=torch.bfloat16``: the update block runs at train precision "bf16" for the call (restored
+        afterwards, also when the call raises) on the bf16 kernels; the hidden states and context terms the front hands it
+        are rounded to bfloat16, values and gradients (``round_gru_inputs_bf16``).  Everything else stays float32.  The range
+        is float32's: step with the plain optimizer, no ``GradScaler``."""
+        if not (amp is False or amp is True or amp is torch.float16 or amp is torch.bfloat16):
+            raise ValueError(f"forward_train: amp must be False, True, torch.float16 or torch.bfloat16, got {amp!r}")
         if not self.training:
             raise _lib.DiffuVolumeError("forward_train is the training entry (model.train()); forward is the eval one")
         if not torch.is_grad_enabled():
@@ -198,11 +206,11 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
                                         "torch.amp.GradScaler")
         if amp:
             before = self.update_block.train_precision
-            self.update_block.set_train_precision("f16")
+            self.update_block.set_train_precision(torch.bfloat16 if amp is torch.bfloat16 else "f16")
             try:
                 return self._forward_train(image1, image2, flow_gt, iters, flow_init, test_mode, t, noise)
             finally:
-                self.update_block.set_train_precision(before)
+                self.update_block.set_train_precision({"bf16": torch.bfloat16}.get(before, before))
         return self._forward_train(image1, image2, flow_gt, iters, flow_init, test_mode, t, noise)
 
     def _forward_train(self, image1, image2, flow_gt, iters, flow_init, test_mode, t, noise):
@@ -215,6 +223,8 @@ class IGEVStereo_ddim(PlanCache, nn.Module):
             # as the inference loop under mixed_precision: the reference's front hands the block fp16 tensors (their
             # gradients pass through the same cast: rounded to fp16, Inf beyond its range -- what GradScaler watches)
             net_list, inp_list = round_gru_inputs_f16(net_list, inp_list)
+        elif self.update_block.train_precision == "bf16":
+            net_list, inp_list = round_gru_inputs_bf16(net_list, inp_list)      # (the same boundary at bf16; no scaler)
         geo, init_disp = self.cost_volume(match_left, match_right, features_left)
         spx_pred = None if test_mode else _spx_init_train(self, features_left[0], stem_2x)
         from .geometry_ddim import Combined_Geo_Encoding_Volume

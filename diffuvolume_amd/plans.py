@@ -559,16 +559,24 @@ class Conv2dF16Plan:
 
     Selected per plan by the update block (never through DV_CONV_PRECISION, which steers the 3-D convolutions).  With
     ``pair=(w2, b2)`` it is the two-gate launch of ConvGRU's convz | convr: ``__call__`` then returns two tensors and takes
-    ``residual`` / ``mul`` as pairs, like Conv2dPairPlan."""
+    ``residual`` / ``mul`` as pairs, like Conv2dPairPlan.
+
+    ``elem``: the 16-bit element type, "f16" (default) or "bf16" -- the same kernel body (csrc/conv2d_mp.h) instantiated on
+    v_mfma_f32_16x16x32_bf16 with bfloat16 rounding (csrc/conv2d_bf16.hip, the entries of
+    include/diffuvolume_hip_amp2d_bf16.h): the update block's train precision "bf16".  The packed image's size and the
+    K-split choice are the fp16 entries': they do not depend on the element type."""
 
     KSPLIT = True
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
-                 pair: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
+                 pair: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, elem: str = "f16"):
+        if elem not in ("f16", "bf16"):
+            raise ValueError(f"Conv2dF16Plan: elem must be 'f16' or 'bf16', got {elem!r}")
+        self.elem = elem
         w = _dev_f32(weight.detach(), "weight")
         self.c1, self.cin, self.k = w.shape[0], w.shape[1], w.shape[2]
         if tuple(w.shape[2:]) != (self.k, self.k) or self.k not in (1, 3):
-            raise _lib.DiffuVolumeError(f"unsupported Conv2d kernel {tuple(w.shape[2:])} for the fp16 path")
+            raise _lib.DiffuVolumeError(f"unsupported Conv2d kernel {tuple(w.shape[2:])} for the {elem} path")
         self.act, self.c2 = act, 0
         biases = [bias]
         if pair is not None:
@@ -584,7 +592,8 @@ class Conv2dF16Plan:
             sizes = [self.c1] + ([self.c2] if pair is not None else [])
             self.bias = torch.cat([_dev_f32(t.detach(), "bias") if t is not None else
                                    torch.zeros(n, dtype=torch.float32, device=w.device) for t, n in zip(biases, sizes)]).contiguous()
-        self.wpacked = pack("dv_conv2d_f16_packed_bytes", "dv_conv2d_f16_pack_weights", w, self.cin, cout, self.k, dtype=torch.uint8)
+        self.wpacked = pack("dv_conv2d_f16_packed_bytes", f"dv_conv2d_{elem}_pack_weights", w, self.cin, cout, self.k,
+                            dtype=torch.uint8)
 
     def __call__(self, x, residual=None, mul=None, blend=None):
         parts = cat_parts(x, self.cin)
@@ -605,14 +614,14 @@ class Conv2dF16Plan:
         nb = 4.0 * (sum(t.numel() for t in parts) + n_out + sum(t.numel() for t in res + mu + [bz, bh] if t is not None))
         # the K-split factor looks at ONE batch item (a shard of a batch reproduces the batch's bits, see Conv2dPlan)
         ks = _lib.load().dv_conv2d_f16_auto_kslices(self.cin, h, w, cout, self.k) if self.KSPLIT else 1
-        tag = f"conv2d_f16_k{self.k}_co{self.c1}" + (f"+{self.c2}" if is_pair else "") + ("_ksplit" if ks > 1 else "")
+        tag = f"conv2d_{self.elem}_k{self.k}_co{self.c1}" + (f"+{self.c2}" if is_pair else "") + ("_ksplit" if ks > 1 else "")
         args = (*cat_args(parts), self.wpacked.data_ptr(), _lib.ptr(self.bias), _lib.ptr(res[0]), _lib.ptr(mu[0]))
         if is_pair:
-            name = "dv_conv2d_f16_cat_pair"
+            name = f"dv_conv2d_{self.elem}_cat_pair"
             args += (outs[0].data_ptr(), _lib.ptr(res[1]), _lib.ptr(mu[1]), outs[1].data_ptr())
             tail = (b, h, w, self.c1, self.c2, self.act)
         else:
-            name = "dv_conv2d_f16_cat"
+            name = f"dv_conv2d_{self.elem}_cat"
             args += (_lib.ptr(bz), _lib.ptr(bh), outs[0].data_ptr())
             tail = (b, h, w, self.c1, self.k, self.act)
         if ks > 1:

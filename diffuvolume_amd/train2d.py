@@ -26,7 +26,12 @@ every plan has an fp16 twin (``f16=True``, the ``plans("train16")`` slot) whose 
 weight gradient runs on ``dv_conv2d_wgrad_cat_f16`` (csrc/conv2d_wgrad_cat_f16.hip, an unrounded float32 dW) and whose gate
 arithmetic rounds like the fp16 epilogues (``dv_gru_reset_mul_f16`` / ``dv_gru_blend_f16``); tensors stay float32 holding
 fp16-exact values, bias gradients stay float32 sums.  ``DV_TRAIN_CONV2D=torch`` at that precision runs the torch
-expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.
+expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.  Train precision "bf16"
+(``set_train_precision(torch.bfloat16)``, ``forward_train(amp=torch.bfloat16)``) is the same route with the other element
+type: every 16-bit plan and function here takes ``elem="bf16"`` beside the ``f16`` flag (``f16=True`` alone means
+``elem="f16"``), the plans live in the ``plans("trainbf16")`` slot and run the bf16 instantiations of the same kernel
+bodies (``Conv2dF16Plan(elem="bf16")``, ``dv_conv2d_wgrad_cat_bf16``, ``dv_gru_reset_mul_bf16`` / ``dv_gru_blend_bf16``,
+``dv_conv2d_1in_bf16``; include/diffuvolume_hip_amp2d_bf16.h); the torch route runs under a real bf16 autocast.
 
 IGEV's convex-upsampling head (``igev_upsample.IGEVUpsampler`` in train mode) uses the third part:
 ``conv_transpose2d_k4`` / ``conv_transpose2d_module``, a ConvTranspose2d(kernel 4, stride 2, padding 1) whose forward is
@@ -133,12 +138,26 @@ def conv2d_module(m: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
 
 # ---- IGEV's update block: convolutions over a virtual concatenation, ConvGRU ----------------------------------------
 
-def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) -> torch.Tensor:
+_ELEM_DTYPE = {"f16": torch.float16, "bf16": torch.bfloat16}
+
+
+def _elem(f16: bool = False, elem: Optional[str] = None) -> Optional[str]:
+    """The 16-bit element type of a plan or call: None (float32), "f16" or "bf16".  ``f16=True`` alone is "f16"; ``elem``
+    names the type beside it."""
+    if elem is None:
+        return "f16" if f16 else None
+    if elem not in _ELEM_DTYPE or (f16 and elem != "f16"):
+        raise ValueError(f"elem must be 'f16' or 'bf16' (and agree with f16={f16!r}), got {elem!r}")
+    return elem
+
+
+def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False, elem: Optional[str] = None) -> torch.Tensor:
     """dW [Cout, sum(c_i), k, k] of a stride-1, dilation-1 convolution (k 3: padding 1) whose input is the channel
     concatenation of ``sources`` (1..4 tensors, never materialised) and whose output gradient is ``g``.  ``f16``: on
     ``dv_conv2d_wgrad_cat_f16`` (both operands rounded to fp16 while staged, fp32 accumulation on the fp16 MFMA, float32
-    result) instead of ``dv_conv2d_wgrad_cat_f32``."""
-    name = "dv_conv2d_wgrad_cat_f16" if f16 else "dv_conv2d_wgrad_cat_f32"
+    result) instead of ``dv_conv2d_wgrad_cat_f32``; ``elem="bf16"``: on ``dv_conv2d_wgrad_cat_bf16``."""
+    e = _elem(f16, elem)
+    name = f"dv_conv2d_wgrad_cat_{e}" if e else "dv_conv2d_wgrad_cat_f32"
     sources = [t.contiguous() for t in sources]
     g = g.contiguous()
     b, cout, h, w = g.shape
@@ -147,7 +166,7 @@ def conv2d_cat_weight_grad(sources, g: torch.Tensor, k: int, f16: bool = False) 
     for t in (*sources, g):
         _lib.check_f32(t, "conv2d_cat_weight_grad operand")
     ptrs, chans, n = cat_args(sources)
-    size = "dv_conv2d_wgrad_cat_f16_workspace_floats" if f16 else "dv_conv2d_wgrad_cat_workspace_floats"
+    size = f"dv_conv2d_wgrad_cat_{e}_workspace_floats" if e else "dv_conv2d_wgrad_cat_workspace_floats"
     ws = _lib.workspace(size, g.device, chans, n, b, h, w, cout, k)
     if ws is None:
         raise _lib.DiffuVolumeError(f"{name} does not take k={k}, channels {list(chans)}, Cout {cout}")
@@ -162,17 +181,18 @@ class _InputGradPlan:
     z | r pair: the gradient then arrives as one tensor per convolution, read as a virtual concatenation).  A
     single-channel gradient (DispHead.conv2, 256 -> 1) runs on ``dv_conv2d_1in_f32``.  ``f16``: the same launch on
     ``Conv2dF16Plan`` / ``dv_conv2d_1in_f16`` -- gradient and weights rounded to fp16, fp32 accumulation, the input gradient
-    rounded to fp16 as the reference's fp16 input gradients are."""
+    rounded to fp16 as the reference's fp16 input gradients are.  ``elem="bf16"``: the bf16 twins."""
 
-    def __init__(self, weights, f16: bool = False):
+    def __init__(self, weights, f16: bool = False, elem: Optional[str] = None):
+        e = _elem(f16, elem)
         w = torch.cat([t.detach() for t in weights], dim=0) if len(weights) > 1 else weights[0].detach()
         self.k = int(w.shape[2])
         wt = (w.transpose(0, 1) if self.k == 1 else w.flip(2, 3).transpose(0, 1)).contiguous()
         self.cin = int(wt.shape[0])
         self.one_in = w.shape[0] == 1 and self.k == 3
         self.wt = wt if self.one_in else None
-        self.fn1 = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
-        self.plan = None if self.one_in else (Conv2dF16Plan(wt, None, act=ACT_NONE) if f16 else
+        self.fn1 = f"dv_conv2d_1in_{e}" if e else "dv_conv2d_1in_f32"
+        self.plan = None if self.one_in else (Conv2dF16Plan(wt, None, act=ACT_NONE, elem=e) if e else
                                               Conv2dPlan(wt, None, dilation=1, act=ACT_NONE))
 
     def __call__(self, grads):
@@ -212,18 +232,19 @@ class TrainConvPlan:
     """One nn.Conv2d (3x3 padding 1, or 1x1; stride 1) of the update block for the training route: the forward plan with
     bias and activation fused, and the packed weights of its input gradient.  ``f16``: the mixed-precision twin (the
     module's ``plans("train16")`` slot) -- forward and input gradient on ``Conv2dF16Plan``, the weight gradient on
-    ``dv_conv2d_wgrad_cat_f16``."""
+    ``dv_conv2d_wgrad_cat_f16``.  ``elem="bf16"``: the bf16 twin (``plans("trainbf16")``)."""
 
-    def __init__(self, conv: torch.nn.Conv2d, act: int, f16: bool = False):
+    def __init__(self, conv: torch.nn.Conv2d, act: int, f16: bool = False, elem: Optional[str] = None):
+        e = _elem(f16, elem)
         k = conv.kernel_size[0]
         if conv.kernel_size != (k, k) or k not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or \
                 conv.padding != ((k - 1) // 2,) * 2 or conv.groups != 1:
             raise _lib.DiffuVolumeError(f"TrainConvPlan: 3x3 (padding 1) or 1x1, stride 1, dilation 1 only, got {conv}")
         _lib.check_f32(conv.weight, "weight")
-        self.k, self.act, self.cout, self.f16 = k, act, conv.out_channels, f16
-        self.fwd = Conv2dF16Plan(conv.weight, conv.bias, act=act) if f16 else \
+        self.k, self.act, self.cout, self.f16, self.elem = k, act, conv.out_channels, e == "f16", e
+        self.fwd = Conv2dF16Plan(conv.weight, conv.bias, act=act, elem=e) if e else \
             Conv2dPlan(conv.weight, None, dilation=1, act=act, bias=conv.bias)
-        self.bwd = _InputGradPlan([conv.weight], f16)
+        self.bwd = _InputGradPlan([conv.weight], elem=e)
 
 
 class ConvCatFn(torch.autograd.Function):
@@ -248,7 +269,7 @@ class ConvCatFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             # (DispHead.conv2, 256 -> 1, idles 63 of the tile's 64 rows; measured at batch 4, 80x184: 0.205 ms here against
             # 0.261 ms on dv_conv2d_wgrad_f32, so it stays on this kernel: a 1 x 2304 reduction is not worth a route)
-            dw = conv2d_cat_weight_grad(sources, gp, plan.k, plan.f16)
+            dw = conv2d_cat_weight_grad(sources, gp, plan.k, elem=plan.elem)
         if ctx.needs_input_grad[2]:
             db = gp.sum(dim=(0, 2, 3))
         dsrc = [None] * len(sources)
@@ -264,10 +285,11 @@ class Conv1InFn(torch.autograd.Function):
     MIOpen's backward-weights of this shape does not return the same bits twice).  The input gradient -- the reference
     always detaches ``disp`` -- is a 64 -> 1 convolution left to PyTorch.  ``f16``: the forward on ``dv_conv2d_1in_f16``;
     the weight gradient stays on the float32 kernel, fed the fp16-rounded ``disp`` (one channel by 49 taps is not an MFMA
-    shape)."""
+    shape).  ``elem="bf16"``: the forward on ``dv_conv2d_1in_bf16``, the weight gradient fed the bf16-rounded ``disp``."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, f16=False):
+    def forward(ctx, x, weight, bias, f16=False, elem=None):
+        e = _elem(f16, elem)
         _lib.check_f32(x, "disp")
         _lib.check_f32(weight, "weight")
         x, wt = x.contiguous(), weight.detach().contiguous()
@@ -276,10 +298,10 @@ class Conv1InFn(torch.autograd.Function):
         if cin != 1 or wt.shape[1] != 1 or k != 7:
             raise _lib.DiffuVolumeError(f"Conv1InFn: one input channel, k = 7, got {tuple(wt.shape)}")
         out = torch.empty((b, wt.shape[0], h, w), dtype=torch.float32, device=x.device)
-        fn = "dv_conv2d_1in_f16" if f16 else "dv_conv2d_1in_f32"
+        fn = f"dv_conv2d_1in_{e}" if e else "dv_conv2d_1in_f32"
         _lib.launch(fn, x.device, x.data_ptr(), wt.data_ptr(), _lib.ptr(bias), out.data_ptr(), b, h, w, out.shape[1], k,
                     ACT_RELU)
-        ctx.save_for_backward(x.half().float() if f16 else x, weight, out)
+        ctx.save_for_backward(x.to(_ELEM_DTYPE[e]).float() if e else x, weight, out)
         return out
 
     @staticmethod
@@ -297,35 +319,39 @@ class Conv1InFn(torch.autograd.Function):
             db = gp.sum(dim=(0, 2, 3))
         if ctx.needs_input_grad[0]:
             dx = F.conv2d(gp, weight.detach().flip(2, 3).transpose(0, 1), None, padding=k // 2)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def _autocast16(fn):
-    """The torch route at "f16" precision: the expression under a real fp16 autocast, the result as float32."""
-    with torch.autocast("cuda", dtype=torch.float16):
+def _autocast16(fn, elem="f16"):
+    """The torch route at "f16" / "bf16" precision: the expression under a real autocast of that dtype, the result as
+    float32."""
+    with torch.autocast("cuda", dtype=_ELEM_DTYPE[elem]):
         return fn().float()
 
 
-def conv_1in_relu(conv: torch.nn.Conv2d, x: torch.Tensor, f16: bool = False) -> torch.Tensor:
+def conv_1in_relu(conv: torch.nn.Conv2d, x: torch.Tensor, f16: bool = False, elem: Optional[str] = None) -> torch.Tensor:
     """relu(conv(x)) for a single-input-channel layer on the training route."""
+    e = _elem(f16, elem)
     if route() == "torch":
-        return _autocast16(lambda: F.relu(conv(x))) if f16 else F.relu(conv(x))
-    return Conv1InFn.apply(x, conv.weight, conv.bias, f16)
+        return _autocast16(lambda: F.relu(conv(x)), e) if e else F.relu(conv(x))
+    return Conv1InFn.apply(x, conv.weight, conv.bias, e == "f16", e)
 
 
-def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources, f16: bool = False) -> torch.Tensor:
+def conv_cat(plan, conv: torch.nn.Conv2d, act: int, sources, f16: bool = False, elem: Optional[str] = None) -> torch.Tensor:
     """act(conv(cat(sources))) for the training route of the update block.  ``plan``: a callable that returns the
     layer's TrainConvPlan; it is only called (and the plan only built) on the HIP route.  ``f16``: the module's train
-    precision is "f16" (the plan is then its fp16 twin; the torch route runs under a real fp16 autocast)."""
+    precision is "f16" (the plan is then its fp16 twin; the torch route runs under a real fp16 autocast); ``elem="bf16"``:
+    the same at "bf16"."""
+    e = _elem(f16, elem)
     sources = list(sources) if isinstance(sources, (list, tuple)) else [sources]
     if route() == "torch":
         def expr():
             x = torch.cat(sources, dim=1) if len(sources) > 1 else sources[0]
             y = F.conv2d(x, conv.weight, conv.bias, padding=(conv.kernel_size[0] - 1) // 2)
             return {ACT_NONE: lambda t: t, ACT_RELU: F.relu, ACT_SIGMOID: torch.sigmoid, ACT_TANH: torch.tanh}[act](y)
-        return _autocast16(expr) if f16 else expr()
+        return _autocast16(expr, e) if e else expr()
     p = plan()
-    assert p.act == act and p.f16 == f16
+    assert p.act == act and p.elem == e
     return ConvCatFn.apply(p, conv.weight, conv.bias, *sources)
 
 
@@ -336,22 +362,23 @@ def _gates(fn: str, *args) -> None:
 class GRUTrainPlan:
     """A ConvGRU for the training route: the z | r pair launch (sigmoid fused, no ``mul``), the candidate's plan (tanh
     fused, no blend) and the packed weights of the two input gradients.  ``f16``: the mixed-precision twin on
-    ``Conv2dF16Plan`` (the z | r pair without ``mul``, the candidate without ``blend``)."""
+    ``Conv2dF16Plan`` (the z | r pair without ``mul``, the candidate without ``blend``); ``elem="bf16"``: the bf16 twin."""
 
-    def __init__(self, gru, f16: bool = False):
+    def __init__(self, gru, f16: bool = False, elem: Optional[str] = None):
+        e = _elem(f16, elem)
         for c in (gru.convz, gru.convr, gru.convq):
             _lib.check_f32(c.weight, "weight")
-        self.hidden, self.f16 = gru.convz.out_channels, f16
-        if f16:
-            self.zr = Conv2dF16Plan(gru.convz.weight, gru.convz.bias, ACT_SIGMOID, pair=(gru.convr.weight, gru.convr.bias))
-            self.q = Conv2dF16Plan(gru.convq.weight, gru.convq.bias, ACT_TANH)
+        self.hidden, self.f16, self.elem = gru.convz.out_channels, e == "f16", e
+        if e:
+            self.zr = Conv2dF16Plan(gru.convz.weight, gru.convz.bias, ACT_SIGMOID, pair=(gru.convr.weight, gru.convr.bias),
+                                    elem=e)
+            self.q = Conv2dF16Plan(gru.convq.weight, gru.convq.bias, ACT_TANH, elem=e)
         else:
             self.zr = Conv2dPairPlan((gru.convz.weight, gru.convz.bias), (gru.convr.weight, gru.convr.bias), ACT_SIGMOID)
             self.q = Conv2dPlan(gru.convq.weight, None, dilation=1, act=ACT_TANH, bias=gru.convq.bias)
-        self.zr_bwd = _InputGradPlan([gru.convz.weight, gru.convr.weight], f16)
-        self.q_bwd = _InputGradPlan([gru.convq.weight], f16)
-        self.mul, self.blend = ("dv_gru_reset_mul_f16", "dv_gru_blend_f16") if f16 else \
-            ("dv_gru_reset_mul_f32", "dv_gru_blend_f32")
+        self.zr_bwd = _InputGradPlan([gru.convz.weight, gru.convr.weight], elem=e)
+        self.q_bwd = _InputGradPlan([gru.convq.weight], elem=e)
+        self.mul, self.blend = f"dv_gru_reset_mul_{e or 'f32'}", f"dv_gru_blend_{e or 'f32'}"
 
 
 class ConvGRUFn(torch.autograd.Function):
@@ -359,7 +386,8 @@ class ConvGRUFn(torch.autograd.Function):
     r*h, no 1-z or z*q.  Inputs: plan, six parameters, h, cz, cr, cq, then the x sources.  The precision is the plan's:
     with an fp16 plan the gate kernels round like conv2d_f16.hip's epilogues (the eval forward's bits under fp16
     autocast), the gate backward stays float32 arithmetic on the fp16-exact saved values (the convolutions that consume
-    its outputs round their operands anyway) and the weight gradients run on ``dv_conv2d_wgrad_cat_f16``."""
+    its outputs round their operands anyway) and the weight gradients run on ``dv_conv2d_wgrad_cat_f16``; a bf16 plan is the
+    same with the bf16 entries."""
 
     @staticmethod
     def forward(ctx, plan, wz, bz, wr, br, wq, bq, h, cz, cr, cq, *xs):
@@ -394,9 +422,9 @@ class ConvGRUFn(torch.autograd.Function):
         dzr_in = plan.zr_bwd([dz, dr])                                # d[h | x...]
         dh += dzr_in[:, :plan.hidden]
         hx = [h, *xs]
-        dwz = conv2d_cat_weight_grad(hx, dz, 3, plan.f16) if need[1] else None
-        dwr = conv2d_cat_weight_grad(hx, dr, 3, plan.f16) if need[3] else None
-        dwq = conv2d_cat_weight_grad([rh, *xs], dq, 3, plan.f16) if need[5] else None
+        dwz = conv2d_cat_weight_grad(hx, dz, 3, elem=plan.elem) if need[1] else None
+        dwr = conv2d_cat_weight_grad(hx, dr, 3, elem=plan.elem) if need[3] else None
+        dwq = conv2d_cat_weight_grad([rh, *xs], dq, 3, elem=plan.elem) if need[5] else None
         dbz = dz.sum(dim=(0, 2, 3)) if need[2] else None
         dbr = dr.sum(dim=(0, 2, 3)) if need[4] else None
         dbq = dq.sum(dim=(0, 2, 3)) if need[6] else None
@@ -409,25 +437,26 @@ class ConvGRUFn(torch.autograd.Function):
                 dr if need[9] else None, dq if need[10] else None, *dxs)
 
 
-def conv_gru(plan, gru, h, cz, cr, cq, *xs, f16: bool = False) -> torch.Tensor:
+def conv_gru(plan, gru, h, cz, cr, cq, *xs, f16: bool = False, elem: Optional[str] = None) -> torch.Tensor:
     """ConvGRU.forward for the training route (the reference's expression under DV_TRAIN_CONV2D=torch; at "f16"
     precision that expression under a real fp16 autocast, on fp16 tensors like the reference's).  ``plan``: a callable
-    that returns the GRUTrainPlan, only called on the HIP route."""
+    that returns the GRUTrainPlan, only called on the HIP route.  ``elem="bf16"``: the same at "bf16"."""
+    e = _elem(f16, elem)
     if route() == "torch":
         def expr():
-            hh, zz, rr, qq = (t.half() for t in (h, cz, cr, cq)) if f16 else (h, cz, cr, cq)
-            x = torch.cat([t.half() for t in xs] if f16 else xs, dim=1)
+            hh, zz, rr, qq = (t.to(_ELEM_DTYPE[e]) for t in (h, cz, cr, cq)) if e else (h, cz, cr, cq)
+            x = torch.cat([t.to(_ELEM_DTYPE[e]) for t in xs] if e else xs, dim=1)
             hx = torch.cat([hh, x], dim=1)
             z = torch.sigmoid(gru.convz(hx) + zz)
             r = torch.sigmoid(gru.convr(hx) + rr)
             q = torch.tanh(gru.convq(torch.cat([r * hh, x], dim=1)) + qq)
             return (1 - z) * hh + z * q
-        return _autocast16(expr) if f16 else expr()
+        return _autocast16(expr, e) if e else expr()
     if len(xs) > 3:                                     # the kernels take four sources: [h | x1 | x2 | x3]
         xs = (torch.cat(xs[:-2], dim=1),) + tuple(xs[-2:])
     c = gru.convz, gru.convr, gru.convq
     p = plan()
-    assert p.f16 == f16
+    assert p.elem == e
     return ConvGRUFn.apply(p, c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias, h, cz, cr, cq, *xs)
 
 

@@ -35,6 +35,16 @@ reference rounds it to fp16), the gate backward in float32 on the fp16-exact sav
 so the precision holds with or without a caller's fp16 autocast; fp16 inputs are converted to float32 once on entry,
 all outputs and gradients are float32, bf16 autocast is refused.  Under ``DV_TRAIN_CONV2D=torch`` that precision runs the
 torch expressions under a real ``torch.autocast("cuda", dtype=torch.float16)``.
+
+``set_train_precision(torch.bfloat16)`` (what ``forward_train(amp=torch.bfloat16)`` sets for the call; ``train_precision``
+then reads "bf16") is the same route on the bf16 matrix instruction: the ``plans("trainbf16")`` slot, the same kernel bodies
+instantiated for bfloat16 (csrc/conv2d_bf16.hip, csrc/conv2d_wgrad_cat_bf16.hip, csrc/gru_gates_bf16.hip,
+``dv_conv2d_1in_bf16``; include/diffuvolume_hip_amp2d_bf16.h) with the rounding points above, rb16 in place of r16 -- what
+``torch.autocast("cuda", dtype=torch.bfloat16)`` does to the block, apart from the unrounded dW and the float32 gate
+backward.  The range is float32's: no ``GradScaler``, no skipped step.  At "bf16" a caller's bf16 autocast is accepted,
+bf16 inputs are converted to float32 once on entry, and fp16 autocast raises.  The method takes "f32", "f16",
+``torch.float32``, ``torch.float16`` and ``torch.bfloat16``; the bare string "bf16" raises ValueError, as on the 3-D models.
+Eval under bf16 autocast stays refused: the reference has no such inference mode.
 """
 from __future__ import annotations
 
@@ -62,29 +72,39 @@ class _Planned(PlanCache, nn.Module):
     """Two plan slots (submodule.PlanCache): the fp32 plans (``plans()``) and the fp16-autocast ones (``plans("f16")``),
     each built lazily by the module's ``_build`` / ``_build16``, and the training route's (``plans("train")``,
     ``_build_train``: forward plans plus the packed weights of the input gradients; ``plans("train16")``: their fp16
-    twins, taken when the module's train precision is "f16")."""
+    twins, taken when the module's train precision is "f16"; ``plans("trainbf16")``: the bf16 twins, at "bf16")."""
 
     _train_precision = "f32"
 
     def _build_plans(self, slot):
-        if slot in ("train", "train16"):
-            return self._build_train(slot == "train16")
+        if slot in _TRAIN_SLOTS.values():
+            return self._build_train(**_SLOT_ARGS[slot])
         return self._build16() if slot == "f16" else self._build()
 
-    def set_train_precision(self, precision: str):
+    def set_train_precision(self, precision):
         """"f32" (default: train mode refuses autocast) or "f16" (mixed-precision training on the fp16 kernels, with or
         without a caller's fp16 autocast) for this module and every module of the block below it -- each is a training
-        entry of its own."""
-        if precision not in ("f32", "f16"):
-            raise ValueError(f"train precision must be 'f32' or 'f16', got {precision!r}")
+        entry of its own.  Also ``torch.float32``, ``torch.float16`` and ``torch.bfloat16``, named as ``torch.autocast``
+        names them; ``train_precision`` then reads "f32", "f16" or "bf16".  ``torch.bfloat16`` is THE spelling of bf16 (the
+        same route on the bf16 kernels, no ``GradScaler``): the bare string "bf16" raises ValueError, as do "fp16", None,
+        16 and any other dtype -- the rule of the 3-D models (``train3d.TrainPrecision``)."""
+        from .train3d import _MODEL_PRECISIONS
+        if isinstance(precision, bool) or not isinstance(precision, (str, torch.dtype)) or precision not in _MODEL_PRECISIONS:
+            raise ValueError('train precision must be "f32", "f16", torch.float32, torch.float16 or torch.bfloat16, '
+                             f"got {precision!r}")
         for m in self.modules():
             if isinstance(m, _Planned):
-                m._train_precision = precision
+                m._train_precision = _MODEL_PRECISIONS[precision]
         return self
 
     @property
     def train_precision(self) -> str:
         return self._train_precision
+
+
+# train precision -> its plan slot, and what ``_build_train`` gets for the slot
+_TRAIN_SLOTS = {"f32": "train", "f16": "train16", "bf16": "trainbf16"}
+_SLOT_ARGS = {"train": {}, "train16": {"f16": True}, "trainbf16": {"elem": "bf16"}}
 
 
 def _plan(conv: nn.Conv2d, act: int) -> Conv2dPlan:
@@ -96,8 +116,8 @@ def _plan16(conv: nn.Conv2d, act: int) -> Conv2dF16Plan:
 
 
 def _f32(t):
-    """fp16 tensors an autocast caller hands over, as float32 (once, on entry)."""
-    return t.float() if isinstance(t, torch.Tensor) and t.dtype == torch.float16 else t
+    """fp16 / bf16 tensors an autocast caller hands over, as float32 (once, on entry)."""
+    return t.float() if isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16) else t
 
 
 class DispHead(_Planned):
@@ -114,16 +134,16 @@ class DispHead(_Planned):
     def _build16(self):
         return _plan16(self.conv1, ACT_RELU), _plan16(self.conv2, ACT_NONE)
 
-    def _build_train(self, f16=False):
+    def _build_train(self, f16=False, elem=None):
         from .train2d import TrainConvPlan
-        return TrainConvPlan(self.conv1, ACT_RELU, f16), TrainConvPlan(self.conv2, ACT_NONE, f16)
+        return TrainConvPlan(self.conv1, ACT_RELU, f16, elem), TrainConvPlan(self.conv2, ACT_NONE, f16, elem)
 
     def forward(self, x):
         if _training(self):
             from .train2d import conv_cat
-            f16, slot = _train_entry(self)
+            e, slot = _train_entry(self)
             return conv_cat(lambda: self.plans(slot)[1], self.conv2, ACT_NONE,
-                            conv_cat(lambda: self.plans(slot)[0], self.conv1, ACT_RELU, _f32(x) if f16 else x, f16), f16)
+                            conv_cat(lambda: self.plans(slot)[0], self.conv1, ACT_RELU, _f32(x) if e else x, elem=e), elem=e)
         c1, c2 = self.plans("f16") if autocast_f16() else self.plans()
         return c2(c1(_f32(x)))
 
@@ -149,18 +169,18 @@ class ConvGRU(_Planned):
         return (Conv2dF16Plan(self.convz.weight, self.convz.bias, ACT_SIGMOID, pair=(self.convr.weight, self.convr.bias)),
                 _plan16(self.convq, ACT_TANH))
 
-    def _build_train(self, f16=False):
+    def _build_train(self, f16=False, elem=None):
         from .train2d import GRUTrainPlan
-        return GRUTrainPlan(self, f16)
+        return GRUTrainPlan(self, f16, elem)
 
     def forward(self, h, cz, cr, cq, *x_list):
         if _training(self):
             from .train2d import conv_gru
-            f16, slot = _train_entry(self)
-            if f16:
+            e, slot = _train_entry(self)
+            if e:
                 h, cz, cr, cq = _f32(h), _f32(cz), _f32(cr), _f32(cq)
                 x_list = tuple(_f32(t) for t in x_list)
-            return conv_gru(lambda: self.plans(slot), self, h, cz, cr, cq, *x_list, f16=f16)
+            return conv_gru(lambda: self.plans(slot), self, h, cz, cr, cq, *x_list, elem=e)
         if autocast_f16():
             # (the fp16 plans round z, r*h and the blend (1-z)*h + z*q at the reference's points; see csrc/conv2d_f16.hip)
             pzr, pq = self.plans("f16")
@@ -214,9 +234,9 @@ class BasicMotionEncoder(_Planned):
                                   torch.cat([b, b.new_zeros(1)]), act=ACT_RELU)
         return p
 
-    def _build_train(self, f16=False):
+    def _build_train(self, f16=False, elem=None):
         from .train2d import TrainConvPlan
-        return {n: TrainConvPlan(getattr(self, n), ACT_RELU, f16) for n in ("convc1", "convc2", "convd2", "conv")}
+        return {n: TrainConvPlan(getattr(self, n), ACT_RELU, f16, elem) for n in ("convc1", "convc2", "convd2", "conv")}
 
     def forward(self, disp, corr):
         return self.features(disp, corr)                # update.py:94 (the reference's return value)
@@ -228,15 +248,15 @@ class BasicMotionEncoder(_Planned):
         bias learn although `disp` is detached."""
         from .geometry_ddim import GeoLookupRequest
         from .train2d import conv_1in_relu, conv_cat
-        f16, slot = _train_entry(self)
+        e, slot = _train_entry(self)
         p = lambda n: (lambda: self.plans(slot)[n])
         if isinstance(corr, GeoLookupRequest):
             corr = corr.materialize()              # the fused lookup + 1x1 is inference-only
-        if f16:
+        if e:
             disp, corr = _f32(disp), _f32(corr)
-        cor = conv_cat(p("convc2"), self.convc2, ACT_RELU, conv_cat(p("convc1"), self.convc1, ACT_RELU, corr, f16), f16)
-        disp_ = conv_cat(p("convd2"), self.convd2, ACT_RELU, conv_1in_relu(self.convd1, disp, f16), f16)
-        out = conv_cat(p("conv"), self.conv, ACT_RELU, [cor, disp_], f16)
+        cor = conv_cat(p("convc2"), self.convc2, ACT_RELU, conv_cat(p("convc1"), self.convc1, ACT_RELU, corr, elem=e), elem=e)
+        disp_ = conv_cat(p("convd2"), self.convd2, ACT_RELU, conv_1in_relu(self.convd1, disp, elem=e), elem=e)
+        out = conv_cat(p("conv"), self.conv, ACT_RELU, [cor, disp_], elem=e)
         return torch.cat([out, disp], dim=1)       # (channel 127: the float32 disp, unrounded, as under autocast)
 
     def features(self, disp, corr):
@@ -296,22 +316,28 @@ def _training(m) -> bool:
 def _train_entry(m):
     """Every module of the block is a training entry of its own (ConvGRU, DispHead, BasicMotionEncoder called directly):
     its train precision decides the route -- "f32" refuses autocast, "f16" takes the fp16 plans with or without the
-    caller's fp16 autocast (bf16 raises) -- and the packed weights follow the weight key, so an optimizer step since the
-    last call drops them here.  Returns (f16, the plan slot)."""
-    f16 = m._train_precision == "f16"
-    if f16:
+    caller's fp16 autocast (bf16 raises), "bf16" takes the bf16 plans with or without the caller's bf16 autocast (fp16
+    raises) -- and the packed weights follow the weight key, so an optimizer step since the last call drops them here.
+    Returns (the 16-bit element type "f16" / "bf16" or None, the plan slot)."""
+    precision = m._train_precision
+    if precision == "f16":
         autocast_f16()                      # (raises on bf16)
+    elif precision == "bf16":
+        if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+            raise _lib.DiffuVolumeError("the update block at train precision 'bf16' takes a caller's bf16 autocast only, got "
+                                        f"{torch.get_autocast_dtype('cuda')}")
     else:
         _no_autocast()
     m.refresh_plans()
-    return f16, ("train16" if f16 else "train")
+    return (None if precision == "f32" else precision), _TRAIN_SLOTS[precision]
 
 
 def _no_autocast():
     if torch.is_autocast_enabled("cuda"):
         raise _lib.DiffuVolumeError("the update block trains in float32 at its default train precision: fp16 / bf16 "
                                     "autocast is not supported in train mode (mixed-precision training: "
-                                    "set_train_precision('f16'), or IGEVStereo_ddim.forward_train(amp=True))")
+                                    "set_train_precision('f16') / set_train_precision(torch.bfloat16), or "
+                                    "IGEVStereo_ddim.forward_train(amp=True) / (amp=torch.bfloat16))")
 
 
 def _hip_ok(x, what):
@@ -375,16 +401,16 @@ class BasicMultiUpdateBlock(_Planned):
     def _build16(self):
         return _plan16(self.mask_feat_4[0], ACT_RELU)
 
-    def _build_train(self, f16=False):
+    def _build_train(self, f16=False, elem=None):
         from .train2d import TrainConvPlan
-        return TrainConvPlan(self.mask_feat_4[0], ACT_RELU, f16)
+        return TrainConvPlan(self.mask_feat_4[0], ACT_RELU, f16, elem)
 
     def _forward_train(self, net, inp, corr, disp, iter04, iter08, iter16, update, mask):
         """The reference's forward (update.py:121-142) on the differentiable route, one stream.  The plans of the whole
         block follow the weight key: an optimizer step between two calls drops them here."""
         from .train2d import conv_cat
-        f16, slot = _train_entry(self)
-        if f16:                   # an autocast caller's fp16 tensors: float32 once, here (the list objects are kept)
+        e, slot = _train_entry(self)
+        if e:                     # an autocast caller's fp16 / bf16 tensors: float32 once, here (the list objects are kept)
             for i in range(len(net)):
                 net[i] = _f32(net[i])
             inp = [[_f32(t) for t in level] for level in inp]
@@ -410,7 +436,7 @@ class BasicMultiUpdateBlock(_Planned):
         if not update:
             return net
         delta_disp = self.disp_head(net[0])
-        mask_feat_4 = conv_cat(lambda: self.plans(slot), self.mask_feat_4[0], ACT_RELU, net[0], f16) if mask else None
+        mask_feat_4 = conv_cat(lambda: self.plans(slot), self.mask_feat_4[0], ACT_RELU, net[0], elem=e) if mask else None
         return net, mask_feat_4, delta_disp
 
     import os as _os

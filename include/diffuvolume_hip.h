@@ -514,7 +514,10 @@ int dv_avg_pool3s2_f32(const float* in, float* out, int BC, int H, int W, dv_str
  *   mul1, the others to out2 with residual2 / mul2.
  * dv_conv2d_f16_auto_kslices: the K-split factor for a launch of this shape (a function of ONE batch item: a shard of a
  *   batch reproduces the batch's bits); > 1 means use the _ksplit forms with scratch of kslices * B * (Cout1 + Cout2)
- *   * H * W floats.  The slices are summed in a fixed order (deterministic). */
+ *   * H * W floats.  The slices are summed in a fixed order (deterministic).
+ * dv_conv2d_f16_packed_bytes and dv_conv2d_f16_auto_kslices serve BOTH 16-bit element types: the bf16 entries of
+ *   diffuvolume_hip_amp2d_bf16.h (csrc/conv2d_bf16.hip, the same kernel body in csrc/conv2d_mp.h) pack an image of the
+ *   same size and take the same launch choice -- neither depends on the element type, so they have no bf16 twins. */
 size_t dv_conv2d_f16_packed_bytes(int Cin, int Cout, int k);
 int dv_conv2d_f16_pack_weights(const float* w, void* wpacked, int Cin, int Cout, int k, dv_stream_t stream);
 int dv_conv2d_f16_auto_kslices(int Cin, int H, int W, int Cout, int k);
@@ -694,7 +697,7 @@ int dv_gru_gates_bwd_reset_f32(const float* drh, const float* r, const float* h,
 int dv_conv2d_1in_wgrad_f32(const float* x, const float* g, float* dw, int B, int H, int W, int Cout, int k,
                             dv_stream_t stream);
 
-/* ---- mixed-precision training of the update block (csrc/conv2d_wgrad_cat_f16.hip) ----------------------
+/* ---- mixed-precision training of the update block (csrc/conv2d_wgrad_cat_f16.hip, body in csrc/conv2d_wgrad_cat_mp.h) ----
  * dv_conv2d_wgrad_cat_f16: the weight gradient of dv_conv2d_wgrad_cat_f32 (same arguments, same virtual concatenation)
  * as KITTI15/core/update.py:26-142 computes it under `autocast(enabled=args.mixed_precision)` (train_stereo.py:146-173):
  *   dw[co, ci, ky, kx] = sum_{b, y, x} r16(g[b, co, y, x]) * r16(X[b, ci, y + ky - p, x + kx - p])

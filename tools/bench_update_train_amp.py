@@ -14,7 +14,13 @@
            amp=False beside amp=True (loss scaled by 1024), alternating, median of three
 No target is fixed.
 
-    python tools/bench_update_train_amp.py [--skip-kernel] [--skip-block] [--skip-step] [--out FILE]"""
+``--bf16`` adds the bf16 arms and writes profiles/update_train_amp_bf16_bench.json instead:
+  kernel   the 384 -> 128 layer alone: dv_conv2d_wgrad_cat_f32, _f16 and _bf16
+  block    the HIP route at "f32", "f16" and "bf16" and the torch autocast routes in fp16 and bf16 (no loss scale at bf16)
+  step     forward_train with amp False / True / torch.bfloat16
+alternating in one process, five runs each, median and min-max.
+
+    python tools/bench_update_train_amp.py [--bf16] [--skip-kernel] [--skip-block] [--skip-step] [--out FILE]"""
 import argparse
 import json
 import os
@@ -81,18 +87,20 @@ def counted_bytes(src, cout, k, b, h, w, splits):
     return planes * (cin * -(-cout // 64) + cout * -(-cin // 64)) + 4.0 * cout * cin * k * k * (2 * splits + 1)
 
 
-def time_kernel(batch, h, w, rounds, reps):
+def time_kernel(batch, h, w, rounds, reps, bf16=False):
     import ctypes
     from diffuvolume_amd import _lib
     out = []
     first = True
-    for name, div, src, cout, k in [("gru04.convz", 1, (128, 128, 128), 128, 3)] + block_layers()[1:]:
+    for name, div, src, cout, k in [("gru04.convz", 1, (128, 128, 128), 128, 3)] + ([] if bf16 else block_layers()[1:]):
         hh, ww = h // div, w // div
         srcs = [torch.randn(batch, c, hh, ww, device="cuda") for c in src]
         g = torch.randn(batch, cout, hh, ww, device="cuda")
         cin = sum(src)
         legs = {"f16": lambda: conv2d_cat_weight_grad(srcs, g, k, f16=True), "f32": lambda: conv2d_cat_weight_grad(srcs, g, k)}
-        if first:
+        if bf16:
+            legs["bf16"] = lambda: conv2d_cat_weight_grad(srcs, g, k, elem="bf16")
+        elif first:
             x16, g16 = torch.cat(srcs, dim=1).half(), g.half()
             legs["miopen_f16"] = lambda: torch.nn.grad.conv2d_weight(x16, (cout, cin, k, k), g16, padding=k // 2)
         arr = (ctypes.c_int * len(src))(*src)
@@ -105,20 +113,26 @@ def time_kernel(batch, h, w, rounds, reps):
         row["f16"]["frac_hbm_8tbs"] = round(nbytes / (row["f16"]["median_ms"] * 1e-3) / HBM, 3)
         row["f32"]["frac_fp32_peak"] = round(flop / (row["f32"]["median_ms"] * 1e-3) / PEAK32, 3)
         row["f16_over_f32"] = round(row["f16"]["median_ms"] / row["f32"]["median_ms"], 3)
-        if first:
+        if bf16:
+            row["bf16"]["frac_bf16_peak"] = round(flop / (row["bf16"]["median_ms"] * 1e-3) / PEAK16, 4)
+            row["bf16_over_f16"] = round(row["bf16"]["median_ms"] / row["f16"]["median_ms"], 3)
+            row["bf16_over_f32"] = round(row["bf16"]["median_ms"] / row["f32"]["median_ms"], 3)
+            row["bf16_median_inside_f16_min_max"] = row["f16"]["min_ms"] <= row["bf16"]["median_ms"] <= row["f16"]["max_ms"]
+        elif first:
             row["f16_over_miopen_f16"] = round(row["f16"]["median_ms"] / row["miopen_f16"]["median_ms"], 3)
             a, m = legs["f16"](), legs["miopen_f16"]().float()
             row["miopen_f16_rel_l2_against_f16"] = float(f"{float((m - a).norm() / a.norm()):.3e}")
         out.append(row)
         print(f"  {name:16s} {hh:3d}x{ww:<3d} f16 {row['f16']['median_ms']:.3f} ms ({row['f16']['frac_fp16_peak']:.4f} of the fp16 "
               f"peak, {row['f16']['frac_hbm_8tbs']:.3f} of 8 TB/s)  f32 {row['f32']['median_ms']:.3f} ms"
-              + (f"  MIOpen fp16 {row['miopen_f16']['median_ms']:.3f} ms" if first else ""), flush=True)
+              + (f"  bf16 {row['bf16']['median_ms']:.3f} ms" if bf16 else "")
+              + (f"  MIOpen fp16 {row['miopen_f16']['median_ms']:.3f} ms" if first and not bf16 else ""), flush=True)
         first = False
         del srcs, g
     return out
 
 
-def time_block(batch, h, w, iters, rounds):
+def time_block(batch, h, w, iters, rounds, bf16=False):
     args = types.SimpleNamespace(**UPDATE_TRAIN_ARGS)
     block = BasicMultiUpdateBlock(args, hidden_dims=UPDATE_TRAIN_HIDDEN)
     block.load_state_dict(synth_state_dict(block.state_dict(), seed=7), strict=True)
@@ -126,6 +140,9 @@ def time_block(batch, h, w, iters, rounds):
     opt = torch.optim.AdamW(block.parameters(), lr=1e-5)
     x = update_train_inputs(41, batch, h, w, iters, device="cuda")
     routes = {"hip_f32": ("hip", "f32", 1.0), "hip_f16": ("hip", "f16", SCALE), "torch_autocast_f16": ("torch", "f16", SCALE)}
+    if bf16:
+        routes = {"hip_f32": routes["hip_f32"], "hip_f16": routes["hip_f16"], "hip_bf16": ("hip", torch.bfloat16, 1.0),
+                  "torch_autocast_f16": routes["torch_autocast_f16"], "torch_autocast_bf16": ("torch", torch.bfloat16, 1.0)}
 
     def step(route):
         env, precision, scale = routes[route]
@@ -156,10 +173,17 @@ def time_block(batch, h, w, iters, rounds):
               f"peak memory {mem[route]} GiB", flush=True)
     rec["hip_f16_over_hip_f32"] = round(rec["hip_f16"]["median_ms"] / rec["hip_f32"]["median_ms"], 3)
     rec["hip_f16_over_torch_autocast"] = round(rec["hip_f16"]["median_ms"] / rec["torch_autocast_f16"]["median_ms"], 3)
+    if bf16:
+        rec["hip_bf16_over_hip_f32"] = round(rec["hip_bf16"]["median_ms"] / rec["hip_f32"]["median_ms"], 3)
+        rec["hip_bf16_over_hip_f16"] = round(rec["hip_bf16"]["median_ms"] / rec["hip_f16"]["median_ms"], 3)
+        rec["hip_bf16_over_torch_autocast_bf16"] = round(rec["hip_bf16"]["median_ms"] / rec["torch_autocast_bf16"]["median_ms"], 3)
+        rec["hip_bf16_median_inside_hip_f16_min_max"] = rec["hip_f16"]["min_ms"] <= rec["hip_bf16"]["median_ms"] <= rec["hip_f16"]["max_ms"]
+        rec["hip_bf16_and_hip_f32_ranges_apart"] = rec["hip_bf16"]["max_ms"] < rec["hip_f32"]["min_ms"] or \
+            rec["hip_f32"]["max_ms"] < rec["hip_bf16"]["min_ms"]
     return rec
 
 
-def time_step(batch, h, w, iters, rounds):
+def time_step(batch, h, w, iters, rounds, bf16=False):
     from diffuvolume_amd.igev_stereo_ddim import Feature, IGEVStereo_ddim
     from diffuvolume_amd.loss import sequence_loss
     args = types.SimpleNamespace(**IGEV_TRAIN_ARGS)
@@ -176,11 +200,13 @@ def time_step(batch, h, w, iters, rounds):
         init, preds = m.forward_train(x["image1"], x["image2"], x["flow_full"], x["flow_gt"], iters=iters, t=x["t"],
                                       noise=x["noise"], amp=amp)
         loss, _ = sequence_loss(preds, init, x["flow_full"], x["valid"], max_disp=args.max_disp)
-        (loss * (SCALE if amp else 1.0)).backward()
+        (loss * (SCALE if amp is True else 1.0)).backward()
         opt.step()
         return float(loss)
 
     legs = {"amp_false": False, "amp_true": True}
+    if bf16:
+        legs["amp_bf16"] = torch.bfloat16
     res, t = dict(batch=batch, plane=[h, w], iters=iters), {n: [] for n in legs}
     for n, amp in legs.items():
         res[f"{n}_first_loss"] = step(amp)
@@ -194,6 +220,11 @@ def time_step(batch, h, w, iters, rounds):
     res["amp_true_over_amp_false"] = round(res["amp_true"]["median_ms"] / res["amp_false"]["median_ms"], 3)
     print(f"  whole step: amp=False {res['amp_false']['median_ms']:.1f} ms, {res['amp_false_peak_gib']} GiB;  amp=True "
           f"{res['amp_true']['median_ms']:.1f} ms, {res['amp_true_peak_gib']} GiB", flush=True)
+    if bf16:
+        res["amp_bf16_over_amp_false"] = round(res["amp_bf16"]["median_ms"] / res["amp_false"]["median_ms"], 3)
+        res["amp_bf16_over_amp_true"] = round(res["amp_bf16"]["median_ms"] / res["amp_true"]["median_ms"], 3)
+        print(f"  whole step: amp=torch.bfloat16 {res['amp_bf16']['median_ms']:.1f} ms ({res['amp_bf16']['min_ms']:.1f}-"
+              f"{res['amp_bf16']['max_ms']:.1f}), {res['amp_bf16_peak_gib']} GiB", flush=True)
     return res
 
 
@@ -209,20 +240,24 @@ def main():
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-block", action="store_true")
     ap.add_argument("--skip-step", action="store_true")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "update_train_amp_bench.json"))
+    ap.add_argument("--bf16", action="store_true", help="add the bf16 arms; five runs of every arm")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.bf16:
+        a.step_rounds = max(a.step_rounds, 5)
+    a.out = a.out or str(ROOT / "profiles" / ("update_train_amp_bf16_bench.json" if a.bf16 else "update_train_amp_bench.json"))
     assert torch.cuda.is_available(), "needs the MI355X"
     rec = dict(device=torch.cuda.get_device_name(0), csrc_sha16=_build.csrc_sha16(), fp16_peak_tflops=PEAK16 / 1e12,
                fp32_peak_tflops=PEAK32 / 1e12)
     if not a.skip_kernel:
         print("weight-gradient kernel, f16 against f32 (and MIOpen fp16 on the largest layer):", flush=True)
-        rec["kernel"] = time_kernel(a.batch, a.height, a.width, a.rounds, a.reps)
+        rec["kernel"] = time_kernel(a.batch, a.height, a.width, a.rounds, a.reps, a.bf16)
     if not a.skip_block:
         print("update-block training step:", flush=True)
-        rec["block"] = time_block(a.batch, a.height, a.width, a.iters, a.rounds)
+        rec["block"] = time_block(a.batch, a.height, a.width, a.iters, a.rounds, a.bf16)
     if not a.skip_step:
         print("whole training step:", flush=True)
-        rec["step"] = time_step(a.batch, 4 * a.height, 4 * a.width, a.iters, a.step_rounds)
+        rec["step"] = time_step(a.batch, 4 * a.height, 4 * a.width, a.iters, a.step_rounds, a.bf16)
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
     print(f"wrote {a.out}")
